@@ -5,7 +5,9 @@ synthetic batch of 256 images per GPU (fp32), inputs resident in HBM before timi
 Multi-GPU: one process per GPU (torchrun), data parallel over RCCL, per-rank batch fixed
 (weak scaling); gradients are averaged with bucketed all-reduces overlapped with backward.
 
-Prints ONE JSON line (rank 0).  Besides the driver's contract fields it carries
+A plain run sets up, warms up, times the K steps, writes its outputs if --dump-outputs DIR is
+given, and prints ONE JSON line (rank 0) with the driver's contract fields (metric, value, unit,
+higher_is_better, dtype, ms_per_step, ...).  With --full the line also carries
   roofline      -- the dominant kernel (largest share of the step, measured with HIP events
                    around every call of that C-ABI entry point during a second run of the K
                    timed steps; `value` comes from the first, uninstrumented run):
@@ -16,6 +18,12 @@ Prints ONE JSON line (rank 0).  Besides the driver's contract fields it carries
   breakdown     -- per entry point: ms per step and roofline fraction (one instrumented step,
                    run single-stream; the timed steps run the weight gradients on a side
                    stream, so the breakdown sums to more than ms_per_step).
+--no-roofline and --cpu-sample 0 switch single legs of a --full run off.
+
+--dump-outputs DIR writes what the last timed step computed as DIR/<name>.npy (float32): what
+the step's caller receives (config 3: `loss`, `probs`) and what it left in the network
+(`param.<layer>.<key>`, `grad.<layer>.<key>`, `state.<layer>.<key>`).  Inputs and initial
+weights are seeded, so two builds run with the same arguments can be compared array for array.
 """
 from __future__ import annotations
 
@@ -39,7 +47,12 @@ def parse():
     ap.add_argument("--warmup", type=int, default=None, help="default 10 (config 2: 20)")
     ap.add_argument("--batch", type=int, default=256, help="images per GPU")
     ap.add_argument("--bn", choices=["local", "sync"], default="local")
-    ap.add_argument("--no-roofline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure what the headline figure does not need: the per-entry breakdown and the "
+                         "dominant kernel's roofline (runs of their own) and the CPU baseline")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write the last step's outputs as DIR/<name>.npy")
+    ap.add_argument("--no-roofline", action="store_true", help="with --full: skip the breakdown and roofline runs")
     ap.add_argument("--cpu-sample", type=int, default=32, help="images per CPU-baseline step (0 = skip)")
     ap.add_argument("--cpu-steps", type=int, default=10, help="timed CPU-baseline steps (median reported)")
     ap.add_argument("--cpu-warmup", type=int, default=2, help="untimed CPU-baseline steps")
@@ -60,6 +73,10 @@ def parse():
         a.steps = 50 if a.config == 2 else 20
     if a.warmup is None:
         a.warmup = 20 if a.config == 2 else 10
+    if a.steps < 1 or a.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
+    a.roofline = a.full and not a.no_roofline
+    a.cpu = a.full and a.cpu_sample > 0
     return a
 
 
@@ -450,6 +467,50 @@ def cpu_baseline_conv(batch=16, steps=5, warmup=1):
                       "{:.1f} s in all".format(steps, batch, warmup, tot)}
 
 
+DUMP_LIMIT_BYTES = 60 * 1000 * 1000  # of the 64 MB a dump may take (the .npy headers come on top)
+
+
+def network_arrays(layers):
+    """{"param.<layer>.<key>" / "grad.<layer>.<key>" / "state.<layer>.<key>": tensor} of every layer
+    (learned parameters, their gradients, BatchNorm's running statistics), composite layers' members
+    and skip projections included."""
+    out = {}
+    for l in layers:
+        for kind, d in (("param", getattr(l, "learned_params", None)), ("grad", getattr(l, "grads", None)),
+                        ("state", getattr(l, "non_learned_params", None))):
+            for k, v in (d or {}).items():
+                if v is not None:
+                    out["{}.{}.{}".format(kind, l.layer_name, k)] = v
+        if hasattr(l, "layer_list"):
+            skip = getattr(l, "skip_projection", None)
+            out.update(network_arrays(list(l.layer_list) + ([skip] if skip is not None else [])))
+    return out
+
+
+def dump_outputs(dirname, arrays, prefix=""):
+    """--dump-outputs: `arrays` ({name: tensor, array or scalar}) as dirname/<prefix><name>.npy in
+    float32 (float64 stays float64).  Above DUMP_LIMIT_BYTES in all, every array keeps the same
+    share of its elements: a fixed sample (flattened, indices drawn with seed 0, ascending)."""
+    import numpy as np
+    import torch
+    torch.cuda.synchronize()
+    host = {}
+    for name, v in arrays.items():
+        if isinstance(v, torch.Tensor):
+            v = v.detach().to("cpu", torch.float64 if v.dtype == torch.float64 else torch.float32).numpy()
+        v = np.asarray(v)
+        host[name] = np.ascontiguousarray(v, dtype=np.float64 if v.dtype == np.float64 else np.float32)
+    total = sum(a.nbytes for a in host.values())
+    os.makedirs(dirname, exist_ok=True)
+    for name, a in sorted(host.items()):
+        if total > DUMP_LIMIT_BYTES:
+            keep = max(1, int(a.size * (DUMP_LIMIT_BYTES / total)))
+            if keep < a.size:
+                idx = np.sort(np.random.default_rng(0).choice(a.size, size=keep, replace=False))
+                a = a.reshape(-1)[idx]
+        np.save(os.path.join(dirname, prefix + name + ".npy"), a)
+
+
 def other_config(args):
     """BASELINE configs 1, 2 and 5 (one GPU): a secondary JSON line each, same timing rules
     (warm-up, then K steps between synchronizations; inputs resident in HBM)."""
@@ -457,6 +518,7 @@ def other_config(args):
     import torch
     from dorknet_amd import perfmodel
     torch.cuda.set_device(0)
+    last = []  # what the latest step returned to its caller
     if args.config == 1:
         from examples.mnist_convnet import MNISTNet
         from dorknet_amd.optimisers.SGDMomentum import SGDMomentum
@@ -470,9 +532,12 @@ def other_config(args):
         Y = torch.as_tensor(np.eye(10, dtype=np.float32)[rng.integers(0, 10, B)], device="cuda")
 
         def step():
-            net.forward(X, Y)
+            last[:] = net.forward(X, Y)
             net.backward()
             sgd.update_weights()
+
+        def outputs():
+            return dict(network_arrays(net.layers), loss=last[0], probs=last[1])
         flops = None
         unit, metric = "images/s", "images/sec training step, MNISTNet bs=64, 1 MI355X (reference: CPU path)"
         dtype, workload = "fp32", "MNISTNet (MNIST_basic_convnet.py:15-69) fwd+loss+bwd+SGD-momentum, BASELINE config 1"
@@ -489,6 +554,11 @@ def other_config(args):
         def step():
             conv.forward(X)
             conv.backward(dY)
+
+        def outputs():
+            # the pass keeps no state, so one more gives what the last timed one gave (the timed
+            # passes drop their two 205 MB results at once, as before)
+            return dict(y=conv.forward(X), dx=conv.backward(dY), **network_arrays([conv]))
         flops = 3 * 2 * B * 56 * 56 * 64 * 64 * 9
         unit, metric = "passes/s", "fwd+dgrad+wgrad passes/sec, ConvLayer(64,64,3,3) s1 p1 on 256x64x56x56"
         dtype, workload = "fp32", "single 3x3 ConvLayer fwd+bwd, BASELINE config 2"
@@ -505,9 +575,12 @@ def other_config(args):
         dY = dY.contiguous(memory_format=torch.channels_last)
 
         def step():
-            net.forward(X, None)
+            last[:] = net.forward(X, None)
             net.backward(dY)
             sgd.update_weights()
+
+        def outputs():
+            return dict(network_arrays(net.layers), y=last[1])
         flops = None
         unit, metric = "images/s", "images/sec training step, MobileNet-style dw+pw stack bs=512 bf16, 1 MI355X"
         dtype, workload = "bf16 (activations stored bf16; pointwise GEMMs on bf16 MFMA with fp32 accumulation; " \
@@ -518,7 +591,7 @@ def other_config(args):
         step()
     torch.cuda.synchronize()
     breakdown, dominant = None, None
-    if not args.no_roofline:
+    if args.roofline:
         # per-entry attribution on one single-stream step, as for config 3
         with single_stream():
             with Instrument(perfmodel.MODEL.keys()) as ins:
@@ -539,6 +612,8 @@ def other_config(args):
     torch.cuda.synchronize()
     elapsed = time.perf_counter() - t0
     per = elapsed / args.steps
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, outputs())
     roof = None
     if dominant:
         ins = Instrument([dominant], reserve=(breakdown[dominant]["calls"] * args.steps + 8))
@@ -560,7 +635,7 @@ def other_config(args):
     if roof:
         out["roofline"] = roof
         out["breakdown"] = breakdown
-    if args.cpu_sample and args.config in (1, 2):
+    if args.cpu and args.config in (1, 2):
         out["cpu_baseline"] = cpu_baseline_mnist() if args.config == 1 else cpu_baseline_conv()
     print(json.dumps(out), flush=True)
 
@@ -646,8 +721,10 @@ def main():
     X, _, onehot = synthetic_batch(args.batch, seed=1000 + rank)
     X, onehot = as_device(X), as_device(onehot)
 
+    last = []  # what the latest step's forward returned to its caller: loss, probabilities
+
     def step():
-        net.forward(X, onehot)
+        last[:] = net.forward(X, onehot)
         if dp is None:
             net.backward()
         else:
@@ -664,7 +741,7 @@ def main():
     barrier()
 
     breakdown, dominant = None, None
-    if not args.no_roofline:
+    if args.roofline:
         # the per-entry attribution step runs single-stream, so each entry's events bracket only
         # its own kernels
         with single_stream():
@@ -692,6 +769,9 @@ def main():
         t = torch.tensor([elapsed], dtype=torch.float64, device="cuda")
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         elapsed = float(t.item())
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, dict(network_arrays(net.layers), loss=last[0], probs=last[1]),
+                     prefix="rank{}.".format(rank) if world > 1 else "")
 
     # roofline: the dominant entry's live call durations from a second run of the same K steps with
     # its calls bracketed by HIP events on the launch stream (the event records cost ~1 % of the
@@ -715,7 +795,7 @@ def main():
     value = world * args.batch * args.steps / elapsed
     ms_per_step = 1e3 * elapsed / args.steps
     cpu = None
-    if rank == 0 and world == 1 and args.cpu_sample > 0:
+    if rank == 0 and world == 1 and args.cpu:
         cpu = cpu_baseline(args.cpu_sample, args.cpu_steps, args.cpu_warmup)
     if rank == 0:
         out = {"metric": METRIC, "value": round(value, 2), "unit": "images/s", "n_gpus": world,

@@ -14,7 +14,7 @@ if [ "${2:-}" != "--skip-tests" ]; then
 fi
 timeout -k 10 200 python -c "import __graft_entry__ as g; g.smoke()" > "$OUT/smoke_$TAG.log" 2>&1
 rc=$?; tail -1 "$OUT/smoke_$TAG.log"; step smoke $rc
-timeout -k 10 400 python bench.py > "$OUT/bench_$TAG.json" 2> "$OUT/bench_$TAG.err"
+timeout -k 10 400 python bench.py --full > "$OUT/bench_$TAG.json" 2> "$OUT/bench_$TAG.err"
 rc=$?; cut -c1-400 "$OUT/bench_$TAG.json"; step bench $rc
 cd /tmp && export TMPDIR=/tmp
 timeout -k 10 300 rocprofv3 --kernel-trace --stats -f csv -d "$OUT/prof_$TAG" -o bench -- \
@@ -37,7 +37,7 @@ step summary3 $?
 python scripts/pmc_summary.py "$OUT/pmc5_$TAG/fetch" "$OUT/pmc5_$TAG/write" --out "$OUT/${TAG}_config5_pmc.json" \
     > "$OUT/${TAG}_config5_pmc_summary.txt" 2>&1
 step summary5 $?
-timeout -k 10 300 python bench.py --config 5 > "$OUT/bench5_$TAG.json" 2> "$OUT/bench5_$TAG.err"
+timeout -k 10 300 python bench.py --full --config 5 > "$OUT/bench5_$TAG.json" 2> "$OUT/bench5_$TAG.err"
 rc=$?; cut -c1-300 "$OUT/bench5_$TAG.json"; step bench5 $rc
-timeout -k 10 300 python bench.py --config 2 > "$OUT/bench2_$TAG.json" 2> "$OUT/bench2_$TAG.err"
+timeout -k 10 300 python bench.py --full --config 2 > "$OUT/bench2_$TAG.json" 2> "$OUT/bench2_$TAG.err"
 rc=$?; cut -c1-300 "$OUT/bench2_$TAG.json"; step bench2 $rc

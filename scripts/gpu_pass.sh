@@ -33,6 +33,6 @@ if [ $SMOKE = 1 ]; then
   rc=$?; tail -1 "$OUT/smoke_$TAG.log"; step smoke $rc
 fi
 for c in $CFGS; do
-  timeout -k 10 400 python bench.py --config $c --cpu-sample 0 > "$OUT/bench${c}_$TAG.json" 2> "$OUT/bench${c}_$TAG.err"
+  timeout -k 10 400 python bench.py --full --config $c --cpu-sample 0 > "$OUT/bench${c}_$TAG.json" 2> "$OUT/bench${c}_$TAG.err"
   rc=$?; cut -c1-500 "$OUT/bench${c}_$TAG.json"; step bench$c $rc
 done

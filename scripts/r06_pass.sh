@@ -26,11 +26,11 @@ for s in "$@"; do
           rc=$?; cat "$OUT/pwd_bench_${TAG}.txt"; step pwdbench $rc;;
     smoke) timeout -k 10 200 python -c "import __graft_entry__ as g; g.smoke()" > "$OUT/smoke_${TAG}.log" 2>&1
           rc=$?; tail -1 "$OUT/smoke_${TAG}.log"; step smoke $rc;;
-    bench) timeout -k 10 400 python bench.py --cpu-sample 0 > "$OUT/bench3_${TAG}.json" 2> "$OUT/bench3_${TAG}.err"
+    bench) timeout -k 10 400 python bench.py --full --cpu-sample 0 > "$OUT/bench3_${TAG}.json" 2> "$OUT/bench3_${TAG}.err"
           rc=$?; cut -c1-300 "$OUT/bench3_${TAG}.json"; step bench $rc;;
-    bench5) timeout -k 10 300 python bench.py --config 5 > "$OUT/bench5_${TAG}.json" 2> "$OUT/bench5_${TAG}.err"
+    bench5) timeout -k 10 300 python bench.py --full --config 5 > "$OUT/bench5_${TAG}.json" 2> "$OUT/bench5_${TAG}.err"
           rc=$?; cut -c1-300 "$OUT/bench5_${TAG}.json"; step bench5 $rc;;
-    bench2) timeout -k 10 300 python bench.py --config 2 > "$OUT/bench2_${TAG}.json" 2> "$OUT/bench2_${TAG}.err"
+    bench2) timeout -k 10 300 python bench.py --full --config 2 > "$OUT/bench2_${TAG}.json" 2> "$OUT/bench2_${TAG}.err"
           rc=$?; cut -c1-300 "$OUT/bench2_${TAG}.json"; step bench2 $rc;;
     prof) (cd /tmp && export TMPDIR=/tmp && timeout -k 10 300 rocprofv3 --kernel-trace --stats -f csv -d "$OUT/prof_$TAG" -o bench -- \
               python "$ROOT/bench.py" --steps 5 --warmup 2 --cpu-sample 0 --no-roofline > "$OUT/prof_bench_$TAG.json" 2> "$OUT/prof_$TAG.err")

@@ -1940,6 +1940,12 @@ DK_API int dk_dwconv_dgrad_stats_rows(int N, int H, int W, int C, int stride) {
   if (stride != 1) return 0;
   return dk_dwconv_fwd_stats_rows(N, H, W, C, 1);
 }
+// The bf16 stride-1 dgrad's rows: it is the bf16 forward launch (dw_dgrad -> launch_dw_fwd with
+// whole output columns per thread), so it writes that launch's rows, not the fp32 dgrad's.
+DK_API int dk_dwconv_dgrad_bf16_stats_rows(int N, int H, int W, int C, int stride) {
+  if (stride != 1) return 0;
+  return dk_dwconv_fwd_bf16_stats_rows(N, H, W, C, 1);
+}
 
 DK_API int dk_dwconv_dgrad_ex_f32(const float* dy, int N, int OH, int OW, int C, const float* w_crs, int R, int S,
                                   int stride, int pad, float* dx, int H, int W, void* ws, size_t ws_bytes,

@@ -33,6 +33,12 @@ DK_API int dk_pwconv_fwd_bf16_stats_rows(int N, int OH, int OW, int K, int C) {
   if (pw_stream_bf16_fwd_ok(K, C, M)) return pw_stream_bf16_fwd_rows(M, K, C);
   return stats_rows(M, K, C, kRowFwdH, kMfBf16);
 }
+// The same for any stride: the streaming kernels take stride 1 only, a strided launch (the
+// N x OH x OW output lattice of a larger input) always runs the tiled engine -- one row per M tile.
+DK_API int dk_pwconv_fwd_bf16_strided_stats_rows(int N, int OH, int OW, int K, int C, int stride) {
+  if (stride == 1) return dk_pwconv_fwd_bf16_stats_rows(N, OH, OW, K, C);
+  return stats_rows(N * OH * OW, K, C, kRowFwdH, kMfBf16);
+}
 
 DK_API int dk_pwconv_fwd_ex_bf16(const bf16_t* x, int N, int H, int W, int C, const float* w_kc, int K, int stride,
                                  const float* bias, bf16_t* y, int OH, int OW, const float* bn_mean,

@@ -409,7 +409,8 @@ class DepthwiseConvLayer(Layer):
         rows = 0
         if bn is not None and R == S:
             if self.stride == 1:
-                rows = lib.dk_dwconv_dgrad_stats_rows(N, H, W, C, 1)
+                # (the bf16 launch runs whole columns per thread: its own, smaller row count)
+                rows = (lib.dk_dwconv_dgrad_bf16_stats_rows if bf else lib.dk_dwconv_dgrad_stats_rows)(N, H, W, C, 1)
             else:
                 rows = lib.dk_dwconv_dgrad_join_rows(N, H, W, C, R, S, self.stride, self.padding)
         if rows and self.padding <= R - 1 and (residual is None or res is not None):

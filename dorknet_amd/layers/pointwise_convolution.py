@@ -97,7 +97,9 @@ class PointwiseConvLayer(Layer):
         bias = self.learned_params["bias"] if self.with_bias else None
         stats = None
         if bn_stats is not None and not test_mode:
-            rows = (lib.dk_pwconv_fwd_bf16_stats_rows if bf else lib.dk_pwconv_fwd_stats_rows)(N, OH, OW, K, Cp)
+            # (bf16: a strided launch never takes the streaming kernels, so the query takes the stride)
+            rows = (lib.dk_pwconv_fwd_bf16_strided_stats_rows(N, OH, OW, K, Cp, s) if bf
+                    else lib.dk_pwconv_fwd_stats_rows(N, OH, OW, K, Cp))
             stats = torch.empty((rows, 2, K), dtype=torch.float64, device=x.device)
         if bn is not None or stats is not None or bf:
             fwd = lib.dk_pwconv_fwd_ex_bf16 if bf else lib.dk_pwconv_fwd_ex_f32

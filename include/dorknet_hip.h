@@ -189,7 +189,11 @@ int dk_dwconv_fwd_join_f32(const float* a, const float* a_mean, const float* a_i
  * like dx), part[rows][2][C] = per-tile (sum g, sum g * x_hat) -- what dk_bn_bwd_partial_f64
  * computes in a separate pass over x and dx (batch_norm.py:125-174).  Consume with
  * dk_bn_bwd_from_partials_f32.  dk_dwconv_dgrad_stats_rows returns 0 (no fused variant)
- * unless stride == 1 and C/4 divides 256.  The dgrad_ex entries also take an optional
+ * unless stride == 1 and C/4 divides 256; dk_dwconv_dgrad_bf16_stats_rows is the same query for
+ * dk_dwconv_dgrad_ex_bf16, whose stride-1 launch runs whole output columns per thread and writes
+ * fewer rows (as dk_dwconv_fwd_bf16_stats_rows; a buffer sized by the fp32 query would keep
+ * unwritten rows).  For stride 2 (either type) the rows are dk_dwconv_dgrad_join_rows.  The
+ * dgrad_ex entries also take an optional
  * `residual` addend (dx = dgrad + residual: the residual join's other gradient term,
  * residual_block.py:94-97; NULL = none) and make the BN part optional (bn_x == NULL). */
 int dk_pwconv_dgrad_stats_rows(int N, int OH, int OW, int K, int C);
@@ -200,6 +204,7 @@ int dk_pwconv_dgrad_ex_f32(const float* dy, int N, int OH, int OW, int K, const 
  * consumer is dk_conv2d_wgrad_bnbwd_narrow_f32 with g_lattice = 2).  Rows: dk_pwconv_dgrad_stats_rows. */
 int dk_pwconv_dgrad_lattice_f32(const float* dy, int N, int OH, int OW, int K, const float* w_kc, int C, int stride, float* dx_lat, const float* bn_x, const float* bn_mean, const float* bn_invstd, const float* bn_gamma, const float* bn_beta, int bn_relu, double* part, void* stream);
 int dk_dwconv_dgrad_stats_rows(int N, int H, int W, int C, int stride);
+int dk_dwconv_dgrad_bf16_stats_rows(int N, int H, int W, int C, int stride);
 int dk_dwconv_dgrad_ex_f32(const float* dy, int N, int OH, int OW, int C, const float* w_crs, int R, int S, int stride, int pad, float* dx, int H, int W, void* ws, size_t ws_bytes, const float* residual, const float* bn_x, const float* bn_mean, const float* bn_invstd, const float* bn_gamma, const float* bn_beta, int bn_relu, double* part, void* stream);
 /* The other side of the same BatchNorm pair: *_dgrad_bnbwd_f32 = a stride-1 layer's input
  * gradient when its OUTPUT fed a BatchNorm (+ReLU).  g is the gradient w.r.t. that BN's
@@ -255,6 +260,9 @@ int dk_bn_bwd_bf16(const uint16_t* x, const uint16_t* dy, int P, int C, const fl
 int dk_relu_fwd_bf16(const uint16_t* x, long long n, uint16_t* y, uint8_t* mask, void* stream);
 int dk_relu_bwd_bf16(const uint16_t* dy, const uint8_t* mask, long long n, uint16_t* dx, void* stream);
 int dk_pwconv_fwd_bf16_stats_rows(int N, int OH, int OW, int K, int C);
+/* dk_pwconv_fwd_ex_bf16 at stride > 1 never takes the streaming kernels (their rows are what the query
+ * above returns for K, C in {64, 128} and the deep shapes): its rows at any stride. */
+int dk_pwconv_fwd_bf16_strided_stats_rows(int N, int OH, int OW, int K, int C, int stride);
 int dk_pwconv_fwd_ex_bf16(const uint16_t* x, int N, int H, int W, int C, const float* w_kc, int K, int stride, const float* bias, uint16_t* y, int OH, int OW, const float* bn_mean, const float* bn_invstd, const float* bn_gamma, const float* bn_beta, int bn_relu, double* stats, void* stream);
 int dk_pwconv_dgrad_ex_bf16(const uint16_t* dy, int N, int OH, int OW, int K, const float* w_kc, int C, int stride, uint16_t* dx, const uint16_t* residual, const uint16_t* bn_x, const float* bn_mean, const float* bn_invstd, const float* bn_gamma, const float* bn_beta, int bn_relu, double* part, void* stream);
 int dk_pwconv_wgrad_bnx_bf16(const uint16_t* dy, const uint16_t* x, int N, int H, int W, int C, int K, int stride, int OH, int OW, const float* w_kc, float l2, float* dw_kc, void* ws, size_t ws_bytes, const float* bn_mean, const float* bn_invstd, const float* bn_gamma, const float* bn_beta, int bn_relu, void* stream);

@@ -279,7 +279,7 @@ def test_bf16_bnbwd_fusions_match_unfused(relu):
     lib.dk_bn_bwd_apply_bf16(x1.data_ptr(), g1.data_ptr(), g1.numel(), C, *(t.data_ptr() for t in po), relu,
                              k12.data_ptr(), dyd.data_ptr(), st)
     nbd = lib.dk_dwconv_dgrad_workspace_bytes(C, 3, 3)
-    rowsd = lib.dk_dwconv_dgrad_stats_rows(N, H, W, C, 1)
+    rowsd = lib.dk_dwconv_dgrad_bf16_stats_rows(N, H, W, C, 1)
     pd0 = torch.zeros((rowsd, 2, C), dtype=torch.float64, device="cuda")
     dxd0 = torch.empty_like(x)
     lib.dk_dwconv_dgrad_ex_bf16(dyd.data_ptr(), N, H, W, C, wd.data_ptr(), 3, 3, 1, 1, dxd0.data_ptr(), H, W,

@@ -12,86 +12,10 @@ import numpy as np
 import pytest
 import torch
 
-from dorknet_amd._hip import DK_FOLDED, lib, stream_handle
+from dorknet_amd._hip import lib, stream_handle
+from tests._partials import _close, bn_params, check_bwd, check_stats, nhwc, vec  # noqa: F401
 
 pytestmark = pytest.mark.gpu
-
-EPS, MOM = 1e-5, 0.9
-
-
-def nhwc(a):
-    return torch.as_tensor(np.ascontiguousarray(a, dtype=np.float32), device="cuda").contiguous(
-        memory_format=torch.channels_last)
-
-
-def vec(a):
-    return torch.as_tensor(np.ascontiguousarray(a, dtype=np.float32), device="cuda")
-
-
-def bn_params(C, rng):
-    return [vec(v) for v in (rng.randn(C) * 0.3, rng.rand(C) + 0.5, 1 + 0.3 * rng.randn(C), 0.2 * rng.randn(C))]
-
-
-class Res:
-    def __init__(self):
-        self.t = torch.zeros(16384, dtype=torch.int32, device="cuda")
-        self.sc = torch.empty(8 << 20, dtype=torch.uint8, device="cuda")
-
-    def args(self):
-        return self.t.data_ptr(), self.t.numel(), self.sc.data_ptr(), self.sc.numel()
-
-
-def _close(a, b, what):
-    a, b = a.double(), b.double()
-    err = float((a - b).abs().max() / (b.abs().max() + 1e-30))
-    assert err <= 1e-6, (what, err)
-
-
-def check_stats(launch, rows, C, P, rng):
-    """launch(part_ptr) -> status of a producer writing part[rows][2][C] (statistics of P pixels)."""
-    res = Res()
-    st = stream_handle()
-    part = torch.full((rows, 2, C), float("nan"), dtype=torch.float64, device="cuda")
-    rm0, rs0 = vec(rng.randn(C)), vec(rng.rand(C) + 0.5)
-    got = [torch.empty(C, device="cuda") for _ in range(3)] + [rm0.clone(), rs0.clone()]
-    assert lib.dk_bn_fold_arm_stats(part.data_ptr(), rows, C, float(P), EPS, MOM, 0, *(t.data_ptr() for t in got),
-                                    *res.args()) == 0
-    assert launch(part.data_ptr()) == DK_FOLDED
-    want = [torch.empty(C, device="cuda") for _ in range(3)] + [rm0.clone(), rs0.clone()]
-    nb = lib.dk_bn_partials_workspace_bytes(rows, C)
-    ws = torch.empty(max(nb, 256), dtype=torch.uint8, device="cuda")
-    tk = torch.zeros(256, dtype=torch.int32, device="cuda")
-    assert lib.dk_bn_stats_from_partials_f32(part.data_ptr(), rows, C, float(P), EPS, MOM, 0,
-                                             *(t.data_ptr() for t in want), ws.data_ptr(), nb, tk.data_ptr(), st) == 0
-    torch.cuda.synchronize()
-    assert torch.isfinite(part).all()
-    for g, w, name in zip(got, want, ("mean", "std", "invstd", "running_mean", "running_std")):
-        _close(g, w, name)
-    assert int(res.t.abs().sum()) == 0, "tickets not left zero"
-    # unarmed: the same launch returns 0
-    assert launch(part.data_ptr()) == 0
-
-
-def check_bwd(launch, rows, C, P):
-    res = Res()
-    st = stream_handle()
-    part = torch.full((rows, 2, C), float("nan"), dtype=torch.float64, device="cuda")
-    got = [torch.empty(C, device="cuda"), torch.empty(C, device="cuda"), torch.empty(2 * C, device="cuda")]
-    assert lib.dk_bn_fold_arm_bwd(part.data_ptr(), rows, C, float(P), *(t.data_ptr() for t in got),
-                                  *res.args()) == 0
-    assert launch(part.data_ptr()) == DK_FOLDED
-    want = [torch.empty(C, device="cuda"), torch.empty(C, device="cuda"), torch.empty(2 * C, device="cuda")]
-    nb = lib.dk_bn_partials_workspace_bytes(rows, C)
-    ws = torch.empty(max(nb, 256), dtype=torch.uint8, device="cuda")
-    tk = torch.zeros(256, dtype=torch.int32, device="cuda")
-    assert lib.dk_bn_bwd_from_partials_f32(part.data_ptr(), rows, C, float(P), *(t.data_ptr() for t in want),
-                                           ws.data_ptr(), nb, tk.data_ptr(), st) == 0
-    torch.cuda.synchronize()
-    assert torch.isfinite(part).all()
-    for g, w, name in zip(got, want, ("dgamma", "dbeta", "k12")):
-        _close(g, w, name)
-    assert int(res.t.abs().sum()) == 0, "tickets not left zero"
-    assert launch(part.data_ptr()) == 0
 
 
 @pytest.mark.parametrize("K,C,N,H,stream", [(64, 64, 32, 56, 1), (64, 64, 2, 5, 1), (64, 64, 256, 56, 0),

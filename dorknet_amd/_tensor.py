@@ -71,7 +71,10 @@ def to_nhwc(x, cpad: int = 1) -> torch.Tensor:
     if x.dtype == BF16:
         # layout plumbing for a bf16 input given in NCHW: a copy into channels_last (+ zero
         # channels), no arithmetic
-        out = torch.zeros((n, cp, h, w), dtype=BF16, device=x.device, memory_format=torch.channels_last)
+        # (torch.zeros takes no memory_format)
+        out = torch.empty((n, cp, h, w), dtype=BF16, device=x.device, memory_format=torch.channels_last)
+        if cp != c:
+            out[:, c:].zero_()
         out[:, :c].copy_(x)
         return out
     if cp == c and x.is_contiguous():

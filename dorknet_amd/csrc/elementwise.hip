@@ -125,21 +125,23 @@ __global__ __launch_bounds__(256) void bn_add_kernel(const float* __restrict__ a
 // out[n][c] = mean_{hw} x[n][hw][c]
 // (the HW loads of a channel are issued eight at a time and added in order: the sum, and so the
 // result, is the one-at-a-time loop's; issued one by one they left the kernel latency-bound)
-__global__ void gap_fwd_kernel(const float* __restrict__ x, int N, int HW, int C, float* __restrict__ out) {
+// (E: the element type of x -- float, or bf16_t widened on load: the same sum in the same order)
+template <class E>
+__global__ void gap_fwd_kernel(const E* __restrict__ x, int N, int HW, int C, float* __restrict__ out) {
   const int i = blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= N * C) return;
   const int n = i / C, c = i - n * C;
-  const float* p = x + (size_t)n * HW * C + c;
+  const E* p = x + (size_t)n * HW * C + c;
   float s = 0.f;
   int k = 0;
   for (; k + 8 <= HW; k += 8) {
     float v[8];
 #pragma unroll
-    for (int u = 0; u < 8; ++u) v[u] = p[(size_t)(k + u) * C];
+    for (int u = 0; u < 8; ++u) v[u] = ld1(p + (size_t)(k + u) * C);
 #pragma unroll
     for (int u = 0; u < 8; ++u) s += v[u];
   }
-  for (; k < HW; ++k) s += p[(size_t)k * C];
+  for (; k < HW; ++k) s += ld1(p + (size_t)k * C);
   out[i] = s / (float)HW;
 }
 
@@ -186,15 +188,18 @@ __global__ __launch_bounds__(256) void gap_join_kernel(const float* __restrict__
 }
 
 // dx[n][hw][c] = (1/HW) * dy[n][c]; gap_bwd4_kernel: four channels per thread (C % 4 == 0, 16-byte aligned)
-__global__ void gap_bwd_kernel(const float* __restrict__ dy, int N, int HW, int C, float* __restrict__ dx) {
+// (O: the element type of dx -- float, or bf16_t: the same product rounded once on store)
+template <class O>
+__global__ void gap_bwd_kernel(const float* __restrict__ dy, int N, int HW, int C, O* __restrict__ dx) {
   const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
   const long long total = (long long)N * HW * C;
   if (i >= total) return;
   const int c = (int)(i % C);
   const int n = (int)(i / ((long long)HW * C));
-  dx[i] = (1.0f / (float)HW) * dy[(size_t)n * C + c];
+  st1(dx + i, (1.0f / (float)HW) * dy[(size_t)n * C + c]);
 }
-__global__ void gap_bwd4_kernel(const float* __restrict__ dy, int N, int HW, int C, float* __restrict__ dx) {
+template <class O>
+__global__ void gap_bwd4_kernel(const float* __restrict__ dy, int N, int HW, int C, O* __restrict__ dx) {
   const int i = blockIdx.x * blockDim.x + threadIdx.x;  // float4 index; N * HW * C < 2^31 (checked)
   const int C4 = C >> 2;
   if (i >= N * HW * C4) return;
@@ -452,7 +457,9 @@ __global__ __launch_bounds__(256) void l2_multi_final_kernel(const double* __res
 }
 
 // Column sums of an [M][N] matrix, stage 1: ws[chunk][n] = sum of rows in the chunk.
-__global__ void colsum_partial_kernel(const float* __restrict__ in, int M, int N, int rpc, double* __restrict__ ws) {
+// (E: the element type of in -- float, or bf16_t widened on load)
+template <class E>
+__global__ void colsum_partial_kernel(const E* __restrict__ in, int M, int N, int rpc, double* __restrict__ ws) {
   const int n = blockIdx.x * blockDim.x + threadIdx.x;
   if (n >= N) return;
   const int r0 = blockIdx.y * rpc, r1 = min(M, r0 + rpc);
@@ -461,11 +468,11 @@ __global__ void colsum_partial_kernel(const float* __restrict__ in, int M, int N
   for (; r + 8 <= r1; r += 8) {  // 8 loads in flight, added in row order
     float v[8];
 #pragma unroll
-    for (int k = 0; k < 8; ++k) v[k] = in[(size_t)(r + k) * N + n];
+    for (int k = 0; k < 8; ++k) v[k] = ld1(in + (size_t)(r + k) * N + n);
 #pragma unroll
     for (int k = 0; k < 8; ++k) s += (double)v[k];
   }
-  for (; r < r1; ++r) s += (double)in[(size_t)r * N + n];
+  for (; r < r1; ++r) s += (double)ld1(in + (size_t)r * N + n);
   ws[(size_t)blockIdx.y * N + n] = s;
 }
 
@@ -601,7 +608,15 @@ DK_API int dk_bn_add_f32(const float* a, const float* a_mean, const float* a_inv
 }
 
 DK_API int dk_gap_fwd_f32(const float* x, int N, int HW, int C, float* out, void* stream) {
-  hipLaunchKernelGGL(gap_fwd_kernel, grid1((long long)N * C), dim3(256), 0, as_stream(stream), x, N, HW, C, out);
+  hipLaunchKernelGGL(gap_fwd_kernel<float>, grid1((long long)N * C), dim3(256), 0, as_stream(stream), x, N, HW, C, out);
+  return launch_status();
+}
+
+// bf16 x -> fp32 means: dk_gap_fwd_f32's sum (fp32, same order) over the widened values
+DK_API int dk_gap_fwd_bf16(const bf16_t* x, int N, int HW, int C, float* out, void* stream) {
+  if (!x || !out || N < 1 || HW < 1 || C < 1 || (long long)N * HW * C >= (1ll << 31)) return DK_ERR_ARGS;
+  hipLaunchKernelGGL(gap_fwd_kernel<bf16_t>, grid1((long long)N * C), dim3(256), 0, as_stream(stream), x, N, HW, C,
+                     out);
   return launch_status();
 }
 
@@ -622,11 +637,23 @@ DK_API int dk_gap_join_fwd_f32(const float* a, const float* a_mean, const float*
 DK_API int dk_gap_bwd_f32(const float* dy, int N, int HW, int C, float* dx, void* stream) {
   if (C % 4 == 0 && (long long)N * HW * C < (1ll << 31) && (reinterpret_cast<uintptr_t>(dy) & 15) == 0 &&
       (reinterpret_cast<uintptr_t>(dx) & 15) == 0)
-    hipLaunchKernelGGL(gap_bwd4_kernel, grid1((long long)N * HW * C / 4), dim3(256), 0, as_stream(stream), dy, N, HW,
-                       C, dx);
+    hipLaunchKernelGGL(gap_bwd4_kernel<float>, grid1((long long)N * HW * C / 4), dim3(256), 0, as_stream(stream), dy, N,
+                       HW, C, dx);
   else
-    hipLaunchKernelGGL(gap_bwd_kernel, grid1((long long)N * HW * C), dim3(256), 0, as_stream(stream), dy, N, HW, C,
-                       dx);
+    hipLaunchKernelGGL(gap_bwd_kernel<float>, grid1((long long)N * HW * C), dim3(256), 0, as_stream(stream), dy, N, HW,
+                       C, dx);
+  return launch_status();
+}
+
+// fp32 dy -> bf16 dx: dk_gap_bwd_f32's product, rounded to bf16 (RNE) on store
+DK_API int dk_gap_bwd_bf16(const float* dy, int N, int HW, int C, bf16_t* dx, void* stream) {
+  if (!dy || !dx || N < 1 || HW < 1 || C < 1 || (long long)N * HW * C >= (1ll << 31)) return DK_ERR_ARGS;
+  if (C % 4 == 0 && (reinterpret_cast<uintptr_t>(dy) & 15) == 0 && (reinterpret_cast<uintptr_t>(dx) & 7) == 0)
+    hipLaunchKernelGGL(gap_bwd4_kernel<bf16_t>, grid1((long long)N * HW * C / 4), dim3(256), 0, as_stream(stream), dy,
+                       N, HW, C, dx);
+  else
+    hipLaunchKernelGGL(gap_bwd_kernel<bf16_t>, grid1((long long)N * HW * C), dim3(256), 0, as_stream(stream), dy, N,
+                       HW, C, dx);
   return launch_status();
 }
 
@@ -689,8 +716,25 @@ DK_API int dk_colsum_f32(const float* in, int M, int N, float* out, void* ws, si
   if (ws_bytes < dk_colsum_workspace_bytes(M, N)) return DK_ERR_WORKSPACE;
   const int chunks = colsum_chunks(M);
   const int rpc = cdiv(M, chunks);
-  hipLaunchKernelGGL(colsum_partial_kernel, dim3(cdiv(N, 256), chunks), dim3(256), 0, as_stream(stream), in, M, N, rpc,
-                     static_cast<double*>(ws));
+  hipLaunchKernelGGL(colsum_partial_kernel<float>, dim3(cdiv(N, 256), chunks), dim3(256), 0, as_stream(stream), in, M,
+                     N, rpc, static_cast<double*>(ws));
+  int rc = launch_status();
+  if (rc) return rc;
+  hipLaunchKernelGGL(colsum_final_kernel, dim3(cdiv(N, 256)), dim3(256), 0, as_stream(stream),
+                     static_cast<const double*>(ws), chunks, N, out);
+  return launch_status();
+}
+
+// Column sums of a bf16 [M][N] matrix (a bf16 dy's bias gradient): fp64 accumulation of the widened
+// values in dk_colsum_f32's order, fp32 result; the workspace layout is dk_colsum_f32's
+// (dk_colsum_workspace_bytes).
+DK_API int dk_colsum_bf16(const bf16_t* in, int M, int N, float* out, void* ws, size_t ws_bytes, void* stream) {
+  if (!in || !out || M < 1 || N < 1) return DK_ERR_ARGS;
+  if (ws_bytes < dk_colsum_workspace_bytes(M, N)) return DK_ERR_WORKSPACE;
+  const int chunks = colsum_chunks(M);
+  const int rpc = cdiv(M, chunks);
+  hipLaunchKernelGGL(colsum_partial_kernel<bf16_t>, dim3(cdiv(N, 256), chunks), dim3(256), 0, as_stream(stream), in, M,
+                     N, rpc, static_cast<double*>(ws));
   int rc = launch_status();
   if (rc) return rc;
   hipLaunchKernelGGL(colsum_final_kernel, dim3(cdiv(N, 256)), dim3(256), 0, as_stream(stream),

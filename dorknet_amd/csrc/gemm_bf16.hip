@@ -1,5 +1,5 @@
-// bf16 pointwise entry points (BASELINE config 5) on the implicit-GEMM engine's bf16 MFMA mode
-// (gemm_engine.h).
+// bf16 pointwise entry points (BASELINE config 5) and bf16 dense-convolution entry points on the
+// implicit-GEMM engine's bf16 MFMA mode (gemm_engine.h).
 #include "gemm_engine.h"
 
 using namespace dk;
@@ -248,4 +248,152 @@ DK_API int dk_pwconv_bwd_bnbwd_bf16(const bf16_t* g, const bf16_t* bn_x, int N, 
                                     part ? &ft : nullptr);
   if (rc) return rc;
   return fold_status(wgrad_reduce(wp, rows, K, C, dw_kc, l2 != 0.f ? w_kc : nullptr, l2, st), part ? ft : FoldTail{});
+}
+
+// ---------------------------------------------------------------------------------------
+// bf16 storage twins of the dense convolution (layers/convolution.py; gemm_conv.hip holds the fp32
+// entries).  x / y / dy / dx bf16 NHWC; weights, bias, BN vectors, statistics and weight gradients
+// fp32; every GEMM runs on v_mfma_f32_32x32x16_bf16 (MF = kMfBf16: both operands rounded to bf16 as
+// they are staged, products exact, fp32 accumulation).
+//
+// Loads: a bf16 bload4e moves 8 bytes = 4 channels.  The reduction index k = (tap, c) advances in
+// steps of 4 and C % 4 == 0, so a 4-group never straddles a tap; a k-tile may, and each 4-group takes
+// its own tap's bounds test (LdImgKC::load), so padding is exactly 0 -- also under BN on load, which
+// transforms in-image elements only (ImgBnDescE).
+//
+// Statistics: taken over the bf16-rounded stored value (EpStoreStatsT<bf16_t>::value4 rounds before
+// it accumulates) -- the rule of dk_pwconv_fwd_ex_bf16 and of every other bf16 producer, so that the
+// following BatchNorm normalises exactly the tensor its consumers read.
+// ---------------------------------------------------------------------------------------
+
+// partial-statistics rows of dk_conv2d_fwd_ex_bf16: one per M tile of the tiled engine
+DK_API int dk_conv2d_fwd_bf16_stats_rows(int N, int OH, int OW, int K, int C, int R, int S) {
+  return stats_rows(N * OH * OW, K, R * S * C, kRowConv, kMfBf16);
+}
+
+DK_API int dk_conv2d_fwd_ex_bf16(const bf16_t* x, int N, int H, int W, int C, const float* w_krsc, int K, int R, int S,
+                                 int stride, int pad, const float* bias, bf16_t* y, int OH, int OW,
+                                 const float* bn_mean, const float* bn_invstd, const float* bn_gamma,
+                                 const float* bn_beta, int bn_relu, double* stats, void* stream) {
+  if (C < 4 || C % 4 || K < 4 || K % 4 || !al8(x) || !al8(y) || !aligned16(w_krsc) || (bias && !aligned16(bias)))
+    return DK_ERR_ARGS;
+  if (N < 1 || R < 1 || S < 1 || stride < 1 || OH < 1 || OW < 1) return DK_ERR_ARGS;
+  if (!fits((size_t)N * H * W * C * 4) || !fits((size_t)N * OH * OW * K * 4)) return DK_ERR_ARGS;
+  const hipStream_t st = as_stream(stream);
+  const int M = N * OH * OW, Ktot = R * S * C;
+  const ImgDescE<bf16_t> a = img_h(x, N, H, W, C, OH, OW, R, S, stride, 1, -pad, M);
+  const MatDesc b = mat(w_krsc, K, Ktot, K);
+  auto run = [&](const auto& da) -> int {
+    using DA = std::decay_t<decltype(da)>;
+    if (stats) {
+      EpStoreStatsT<bf16_t> ep{};
+      ep.out = y, ep.ldo = K, ep.bias = bias, ep.v4 = 1, ep.res = nullptr, ep.part = stats;
+      return igemm_rows<LdImgKC, DA, LdMatKC, MatDesc, EpStoreStatsT<bf16_t>, kRowConv, kMfBf16>(da, b, ep, M, K, Ktot,
+                                                                                                 st);
+    }
+    EpStoreT<bf16_t> ep{y, K, bias, 1, nullptr};
+    return igemm_rows<LdImgKC, DA, LdMatKC, MatDesc, EpStoreT<bf16_t>, kRowConv, kMfBf16>(da, b, ep, M, K, Ktot, st);
+  };
+  if (bn_mean) {
+    // (the LDS parameter table holds <= 2048 channels)
+    if (!bn_ok(bn_mean, bn_invstd, bn_gamma, bn_beta) || C > 2048) return DK_ERR_ARGS;
+    return run(with_bn(a, bn_mean, bn_invstd, bn_gamma, bn_beta, bn_relu));
+  }
+  return run(a);
+}
+
+// Stride-1 dgrad (dk_conv2d_dgrad_f32's view): dx[n,h,w,c] = sum_{r,s,k} dy[n, h+pad-r, w+pad-s, k] * w[k][c][r][s]
+DK_API int dk_conv2d_dgrad_bf16(const bf16_t* dy, int N, int OH, int OW, int K, const float* w_crsk, int C, int R,
+                                int S, int pad, bf16_t* dx, int H, int W, void* stream) {
+  if (K < 4 || K % 4 || C < 1 || N < 1 || R < 1 || S < 1 || !al8(dy) || !aligned16(w_crsk) || !dx) return DK_ERR_ARGS;
+  if (!fits((size_t)N * OH * OW * K * 4) || !fits((size_t)N * H * W * C * 4)) return DK_ERR_ARGS;
+  const int M = N * H * W, Ktot = R * S * K;
+  const ImgDescE<bf16_t> a = img_h(dy, N, OH, OW, K, H, W, R, S, 1, -1, pad, M);
+  const MatDesc b = mat(w_crsk, C, Ktot, C);
+  EpStoreT<bf16_t> ep{dx, C, nullptr, al4(C) && al8(dx), nullptr};
+  return igemm_rows<LdImgKC, ImgDescE<bf16_t>, LdMatKC, MatDesc, EpStoreT<bf16_t>, kRowConv, kMfBf16>(
+      a, b, ep, M, C, Ktot, as_stream(stream));
+}
+
+// Any-stride dgrad, one implicit GEMM per sub-pixel phase (dk_conv2d_dgrad_phase_f32's geometry and
+// workspace: the fp32 phase sub-filters of w_phase_kernel); dy has Kp = K rounded up to 4 channels.
+DK_API int dk_conv2d_dgrad_phase_bf16(const bf16_t* dy, int N, int OH, int OW, int Kp, int K, const float* w_kcrs,
+                                      int C, int R, int S, int stride, int pad, bf16_t* dx, int H, int W, void* ws,
+                                      size_t ws_bytes, void* stream) {
+  if (Kp % 4 || Kp < K || K < 1 || stride < 1 || stride > 8 || N < 1 || C < 1 || R < 1 || S < 1 || !al8(dy) || !dx ||
+      !aligned16(ws))
+    return DK_ERR_ARGS;
+  if (ws_bytes < dk_conv2d_dgrad_phase_workspace_bytes(K, C, R, S, stride) || Kp != (K + 3) / 4 * 4)
+    return DK_ERR_WORKSPACE;
+  if (!fits((size_t)N * OH * OW * Kp * 4) || !fits((size_t)N * H * W * C * 4)) return DK_ERR_ARGS;
+  const hipStream_t st = as_stream(stream);
+  float* wsub = static_cast<float*>(ws);
+  int rc = launch_w_phase(w_kcrs, K, C, R, S, stride, pad, Kp, wsub, st);
+  if (rc) return rc;
+  for (int a = 0; a < stride; ++a)
+    for (int b = 0; b < stride; ++b) {
+      const PhaseAxis pa = phase_axis(a, R, stride, pad, H), pb = phase_axis(b, S, stride, pad, W);
+      if (pa.Op == 0 || pb.Op == 0) continue;  // no dx pixels of this phase
+      const int M = N * pa.Op * pb.Op;
+      ImgDescE<bf16_t> d = img_h(dy, N, OH, OW, Kp, pa.Op, pb.Op, pa.Rp, pb.Rp, 1, -1, pa.nb0, M);
+      d.offw = pb.nb0;
+      const int Ktot = pa.Rp * pb.Rp * Kp;
+      const float* wp = wsub + phase_block_offset(a, b, C, R, S, stride, pad, Kp);
+      MatDesc bm = mat(wp, C, Ktot > 0 ? Ktot : 4, C);
+      EpPhaseT<bf16_t> ep{dx, C, pa.Op, pb.Op, H, W, stride, a, b, al4(C) && al8(dx)};
+      rc = igemm_rows<LdImgKC, ImgDescE<bf16_t>, LdMatKC, MatDesc, EpPhaseT<bf16_t>, kRowConv, kMfBf16>(d, bm, ep, M, C,
+                                                                                                       Ktot, st);
+      if (rc) return rc;
+    }
+  return 0;
+}
+
+// Weight gradient: dw[k][c][r][s] = sum_{n,oh,ow} dy[n,oh,ow,k] * bn(x)[n, oh*stride + r - pad, ow*stride + s - pad, c]
+// (+ l2 * w), split-K over the pixels into fp32 slabs, then the fixed-order reduce that also drops
+// the channel padding (Cp -> C) -- the fp32 wgrad() helper's steps with bf16 operands.
+DK_API size_t dk_conv2d_wgrad_bf16_workspace_bytes(int N, int OH, int OW, int K, int Cp, int R, int S) {
+  return splitk_ws_bytes(K, R * S * Cp, N * OH * OW, kMfBf16);
+}
+
+namespace dk {
+template <class D>
+static int wgrad_h(const bf16_t* dy, const D& b, int K, int Ncol, const float* w, float l2, float* dw, int C, int Cp,
+                   int R, int S, void* ws, size_t ws_bytes, void* stream) {
+  const int Kred = b.M;
+  if (!fits((size_t)Kred * K * 4)) return DK_ERR_ARGS;
+  if (ws_bytes < splitk_ws_bytes(K, Ncol, Kred, kMfBf16)) return DK_ERR_WORKSPACE;
+  const MatDescE<bf16_t> a = mat_h(dy, Kred, K, K);
+  int splits = 1;
+  float* part = static_cast<float*>(ws);
+  const hipStream_t st = as_stream(stream);
+  int rc = igemm_splitk<LdMatIC, MatDescE<bf16_t>, LdImgIC, D, kMfBf16>(a, b, part, K, Ncol, Kred, st, &splits);
+  if (rc) return rc;
+  return splitk_reduce(part, splits, K, Ncol, dw, w, l2, 1, C, Cp, R, S, st);
+}
+static inline bool wgrad_h_ok(const bf16_t* dy, const bf16_t* x, int N, int H, int W, int Cp, int C, int K, int R,
+                              int S, int stride, const float* dw, const void* ws) {
+  return Cp >= 4 && Cp % 4 == 0 && C >= 1 && C <= Cp && K >= 4 && K % 4 == 0 && N >= 1 && R >= 1 && S >= 1 &&
+         stride >= 1 && al8(x) && al8(dy) && dw && aligned16(ws) && fits((size_t)N * H * W * Cp * 4);
+}
+}  // namespace dk
+
+DK_API int dk_conv2d_wgrad_bf16(const bf16_t* dy, const bf16_t* x, int N, int H, int W, int Cp, int C, int K, int R,
+                                int S, int stride, int pad, int OH, int OW, const float* w_kcrs, float l2,
+                                float* dw_kcrs, void* ws, size_t ws_bytes, void* stream) {
+  if (!wgrad_h_ok(dy, x, N, H, W, Cp, C, K, R, S, stride, dw_kcrs, ws)) return DK_ERR_ARGS;
+  return wgrad_h(dy, img_h(x, N, H, W, Cp, OH, OW, R, S, stride, 1, -pad, N * OH * OW), K, R * S * Cp, w_kcrs, l2,
+                 dw_kcrs, C, Cp, R, S, ws, ws_bytes, stream);
+}
+
+DK_API int dk_conv2d_wgrad_bnx_bf16(const bf16_t* dy, const bf16_t* x, int N, int H, int W, int Cp, int C, int K,
+                                    int R, int S, int stride, int pad, int OH, int OW, const float* w_kcrs, float l2,
+                                    float* dw_kcrs, void* ws, size_t ws_bytes, const float* bn_mean,
+                                    const float* bn_invstd, const float* bn_gamma, const float* bn_beta, int bn_relu,
+                                    void* stream) {
+  if (!wgrad_h_ok(dy, x, N, H, W, Cp, C, K, R, S, stride, dw_kcrs, ws)) return DK_ERR_ARGS;
+  if (!bn_ok(bn_mean, bn_invstd, bn_gamma, bn_beta)) return DK_ERR_ARGS;
+  return wgrad_h(dy,
+                 with_bn(img_h(x, N, H, W, Cp, OH, OW, R, S, stride, 1, -pad, N * OH * OW), bn_mean, bn_invstd,
+                         bn_gamma, bn_beta, bn_relu),
+                 K, R * S * Cp, w_kcrs, l2, dw_kcrs, C, Cp, R, S, ws, ws_bytes, stream);
 }

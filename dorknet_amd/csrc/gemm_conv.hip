@@ -55,6 +55,14 @@ __global__ void w_phase_kernel(const float* __restrict__ w, int K, int C, int R,
       k < K ? w[(((size_t)k * C + c) * R + r) * S + s_] : 0.f;
 }
 
+int launch_w_phase(const float* w_kcrs, int K, int C, int R, int S, int stride, int pad, int Kp, float* ws,
+                   hipStream_t st) {
+  const int total = C * R * S * Kp;
+  hipLaunchKernelGGL(w_phase_kernel, dim3(cdiv(total, 256)), dim3(256), 0, st, w_kcrs, K, C, R, S, stride, pad, Kp,
+                     ws);
+  return launch_status();
+}
+
 }  // namespace dk
 
 // Tuning knobs (knobs.hip): kind = the KnobId; cfg = -1 restores the default.
@@ -126,20 +134,6 @@ DK_API int dk_conv2d_dgrad_f32(const float* dy, int N, int OH, int OW, int K, co
   return igemm_rows<LdImgKC, ImgDesc, LdMatKC, MatDesc, EpStore>(a, b, ep, N * H * W, C, Ktot, as_stream(stream));
 }
 
-// Sub-pixel phase geometry of a stride-st, pad-p correlation's input gradient along one axis:
-// phase a's taps are r0 + st*t (t < Rp), reading dy row i + nb0 - t for dx row st*i + a.
-struct PhaseAxis {
-  int r0, Rp, nb0, Op;
-};
-static inline PhaseAxis phase_axis(int a, int R, int st, int pad, int L) {
-  PhaseAxis p;
-  p.r0 = phase_r0(a, st, pad);
-  p.Rp = phase_taps(a, R, st, pad);
-  p.nb0 = (a + pad - p.r0) / st;
-  p.Op = a < L ? (L - a + st - 1) / st : 0;
-  return p;
-}
-
 DK_API size_t dk_conv2d_dgrad_phase_workspace_bytes(int K, int C, int R, int S, int stride) {
   if (K < 1 || C < 1 || R < 1 || S < 1 || stride < 1) return 0;
   const size_t kp = (size_t)((K + 3) / 4 * 4);
@@ -161,10 +155,7 @@ DK_API int dk_conv2d_dgrad_phase_f32(const float* dy, int N, int OH, int OW, int
   if (!fits((size_t)N * OH * OW * Kp * 4) || !fits((size_t)N * H * W * C * 4)) return DK_ERR_ARGS;
   const hipStream_t st = as_stream(stream);
   float* wsub = static_cast<float*>(ws);
-  const int total = C * R * S * Kp;
-  hipLaunchKernelGGL(w_phase_kernel, dim3(cdiv(total, 256)), dim3(256), 0, st, w_kcrs, K, C, R, S, stride, pad, Kp,
-                     wsub);
-  int rc = launch_status();
+  int rc = launch_w_phase(w_kcrs, K, C, R, S, stride, pad, Kp, wsub, st);
   if (rc) return rc;
   for (int a = 0; a < stride; ++a)
     for (int b = 0; b < stride; ++b) {

@@ -766,9 +766,11 @@ struct EpPartial {
 
 // The output rows of one sub-pixel phase (a, b) of a stride-st input gradient: GEMM row
 // m = (n, i, j) of an OHp x OWp grid is dx pixel (n, st*i + a, st*j + b) of an H x W image.
-struct EpPhase {
+// O: output element type (float, or bf16_t: rounded on store).
+template <class O>
+struct EpPhaseT {
   static constexpr bool kColStats = false;
-  float* out;
+  O* out;
   int ldo;
   int OHp, OWp, H, W, st, a, b;
   int v4;
@@ -785,9 +787,10 @@ struct EpPhase {
     st4(out + pix(m) * ldo + n, v);
   }
   __device__ __forceinline__ void put1(int m, int n, float v, int, double&, double&) const {
-    out[pix(m) * ldo + n] = v;
+    st1(out + pix(m) * ldo + n, v);
   }
 };
+using EpPhase = EpPhaseT<float>;
 
 // ----------------------------------------------------------------------------
 // The kernel
@@ -1208,6 +1211,13 @@ static inline int row_config(int M, int N, int K, int kind = kRowPlain, int mf =
     // more MFMAs per dependent load round trip
     if (kind == kRowBnBwd) return N <= 128 ? 16 : (N <= 256 ? (K >= 512 ? 13 : 16) : 13);
     if (kind == kRowFwdH && N >= 256) return (K >= 512 && N >= 512) ? 16 : 13;
+    // bf16 dense convolution forward / dgrad (dk_conv2d_fwd_ex_bf16, _dgrad_bf16, _dgrad_phase_bf16),
+    // started from the pointwise rules above (128-column / 8-wave tiles) and measured with
+    // scripts/conv_bf16_bench.py --sweep (profiles/conv_bf16_bench.md, config 2's 3x3 64 -> 64 on
+    // 256 x 56 x 56: 128x64x32 with 2x2 waves 137.5 us forward / 138.1 us dgrad, next 64x64x32 155 us;
+    // profiles/conv_bf16_bench_128.md, 3x3 128 -> 128 on 256 x 28 x 28: 128x128x32 with 2x4 waves
+    // 128.7 / 129.2 us, next 64x128x32 135 us)
+    if (kind == kRowConv && K > 128) return N >= 128 ? 16 : 15;  // 128x128x32 (2x4 waves) / 128x64x32 (2x2)
   }
   if (kind == kRowFwdH) kind = kRowPlain;
   if (kind == kRowBnBwd) {
@@ -1247,6 +1257,11 @@ static inline int splitk_config(int M, int N, int Kred, int mf = kMfF32) {
   (void)Kred;
   // bf16 MFMA: 128 x 128 tiles for the 14 x 14 / 7 x 7 weight gradients (profiles/r03k_bf16_gemm_tune.txt)
   if (mf == kMfBf16 && M >= 128 && N >= 128) return 4;
+  // bf16 conv-shaped weight gradient (dk_conv2d_wgrad_bf16: M = K filters <= 64 < N = R*S*Cp columns):
+  // the fp32 rule below (64x128x32) holds for bf16 too -- config 2's 3x3 conv (M = 64, N = 576): 181.9 us
+  // against 228.8 (64x64x64) and 230.9 (64x64x32), scripts/conv_bf16_bench.py --sweep,
+  // profiles/conv_bf16_bench.md
+  if (mf == kMfBf16 && M <= 64 && N > 64) return 6;
   // Wide column tiles when M <= 64 < N: the A operand (for the stem the BN-backward-on-load dy,
   // formed from 2 x 822 MB) is streamed half as often -- the stem (N = R*S*Cp = 100) in one
   // column tile; BASELINE config 2's 3x3 conv (N = 576): 594 vs 628 us (profiles/r01j_gemm_tune_all.txt).
@@ -1310,6 +1325,23 @@ __host__ __device__ __forceinline__ size_t phase_block_offset(int a, int b, int 
     off += (size_t)C * phase_taps(i / st, R, st, pad) * phase_taps(i % st, S, st, pad) * Kp;
   return off;
 }
+
+// Sub-pixel phase geometry of a stride-st, pad-p correlation's input gradient along one axis:
+// phase a's taps are r0 + st*t (t < Rp), reading dy row i + nb0 - t for dx row st*i + a.
+struct PhaseAxis {
+  int r0, Rp, nb0, Op;
+};
+static inline PhaseAxis phase_axis(int a, int R, int st, int pad, int L) {
+  PhaseAxis p;
+  p.r0 = phase_r0(a, st, pad);
+  p.Rp = phase_taps(a, R, st, pad);
+  p.nb0 = (a + pad - p.r0) / st;
+  p.Op = a < L ? (L - a + st - 1) / st : 0;
+  return p;
+}
+// The phase sub-filters of w_kcrs into ws (w_phase_kernel, gemm_conv.hip): C * R * S * Kp floats.
+int launch_w_phase(const float* w_kcrs, int K, int C, int R, int S, int stride, int pad, int Kp, float* ws,
+                   hipStream_t st);
 
 
 // rows x ld matrix; ext = extent of the non-reduction index (rows for a K-contiguous

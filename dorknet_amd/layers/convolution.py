@@ -5,7 +5,9 @@ materialises a [N*OH*OW, C*R*S] patch matrix (convolution.py:69-74), multiplies 
 the flattened filters (:75), and in backward multiplies again and scatters the result
 back with atomics (:101-111).  Here the same contraction runs as an implicit GEMM on the
 fp32 MFMA units: patches are gathered straight from the NHWC activation into LDS tiles
-and never exist in HBM (dk_conv2d_fwd_f32 / _dgrad_f32 / _wgrad_f32).  A narrow input (C <= 4:
+and never exist in HBM (dk_conv2d_fwd_f32 / _dgrad_f32 / _wgrad_f32).  A bf16 input takes the
+bf16-storage twins (dk_conv2d_*_bf16: bf16 activations and gradients, fp32 weights and weight
+gradients, bf16 MFMA; always the implicit-GEMM path, channel-padded to 4).  A narrow input (C <= 4:
 the stem on the 3-channel image) takes the narrow-input kernels instead, which read the NCHW
 image as given and reduce over k = (c, r, s) without channel padding (dk_conv2d_*_narrow_f32).
 
@@ -22,7 +24,7 @@ import torch
 
 from .._env import getenv
 from .._hip import lib, stream_handle, weight_grad_stream, workspace
-from .._tensor import as_device, empty_nhwc, ptr, to_nhwc
+from .._tensor import BF16, as_device, empty_nhwc, ptr, to_nhwc
 from ._bn_input import BNGrad, BNOut
 from ._common import add_regulariser_grad, grad_buffer, init_weights, l2_strength
 from .layer import Layer
@@ -126,21 +128,26 @@ class ConvLayer(Layer):
         N, Cp, H, W = x.shape
         K, C, R, S = self.num_filters, self.filter_chans, self.f_rows, self.f_cols
         OH, OW = self._out_size(H, W)
+        bf = x.dtype == BF16  # bf16 storage: the _bf16 entry points
+        if bf and K % 4:
+            raise NotImplementedError("ConvLayer {}: bf16 storage needs a multiple of 4 filters, got {}".format(
+                self.layer_name, K))
         w = self.learned_params["weights"]
         w_krsc = torch.empty((K, R, S, Cp), dtype=torch.float32, device=x.device)
         lib.dk_conv_weight_krsc_f32(w.data_ptr(), K, C, R, S, Cp, w_krsc.data_ptr(), st)
-        y = empty_nhwc(N, K, OH, OW)
+        y = empty_nhwc(N, K, OH, OW, x.dtype)
         bias = self.learned_params["bias"] if self.with_bias else None
         stats = None
         if bn_stats is not None and not test_mode:
-            rows = lib.dk_conv2d_fwd_stats_rows(N, OH, OW, K, Cp, R, S)
+            rows = (lib.dk_conv2d_fwd_bf16_stats_rows if bf else lib.dk_conv2d_fwd_stats_rows)(N, OH, OW, K, Cp, R, S)
             stats = torch.empty((rows, 2, K), dtype=torch.float64, device=x.device)
-        if bn is not None or stats is not None:
+        if bn is not None or stats is not None or bf:
+            fwd = lib.dk_conv2d_fwd_ex_bf16 if bf else lib.dk_conv2d_fwd_ex_f32
             if stats is not None:
                 bn_stats.arm(stats, N * OH * OW)
-            r = lib.dk_conv2d_fwd_ex_f32(x.data_ptr(), N, H, W, Cp, w_krsc.data_ptr(), K, R, S, self.stride,
-                                         self.padding, ptr(bias), y.data_ptr(), OH, OW,
-                                         *(bn.bn_args() if bn is not None else (0, 0, 0, 0, 0)), ptr(stats), st)
+            r = fwd(x.data_ptr(), N, H, W, Cp, w_krsc.data_ptr(), K, R, S, self.stride,
+                    self.padding, ptr(bias), y.data_ptr(), OH, OW,
+                    *(bn.bn_args() if bn is not None else (0, 0, 0, 0, 0)), ptr(stats), st)
             if stats is not None:
                 bn_stats.launched(stats, r)
         else:
@@ -214,6 +221,11 @@ class ConvLayer(Layer):
         st = stream_handle()
         dy = to_nhwc(upstream_dx)
         x = self.X
+        if x.dtype == BF16 or dy.dtype == BF16:
+            if x.dtype != dy.dtype:
+                raise NotImplementedError("ConvLayer {}: the gradient ({}) must have the stored input's type ({})".format(
+                    self.layer_name, dy.dtype, x.dtype))
+            return self._backward_bf16(dy, need_dx, st)
         N, Cp, H, W = x.shape
         K, C, R, S = self.num_filters, self.filter_chans, self.f_rows, self.f_cols
         OH, OW = int(self.num_row_patches), int(self.num_col_patches)
@@ -272,6 +284,52 @@ class ConvLayer(Layer):
             nb = lib.dk_conv2d_dgrad_phase_workspace_bytes(K, C, R, S, self.stride)
             lib.dk_conv2d_dgrad_phase_f32(dyp.data_ptr(), N, OH, OW, Kp, K, w.data_ptr(), C, R, S, self.stride,
                                           self.padding, dx.data_ptr(), Hin, Win, workspace.get(nb), nb, st)
+        return dx
+
+    def _backward_bf16(self, dy, need_dx, st):
+        """bf16 storage: dy and the stored input are bf16 (the input channel-padded to Cp), the
+        parameter gradients fp32, dx bf16 with the forward input's shape."""
+        x = self.X
+        N, Cp, H, W = x.shape
+        K, C, R, S = self.num_filters, self.filter_chans, self.f_rows, self.f_cols
+        OH, OW = int(self.num_row_patches), int(self.num_col_patches)
+        w = self.learned_params["weights"]
+        P = N * OH * OW
+        if tuple(dy.shape) != (N, K, OH, OW):
+            raise ValueError("ConvLayer {}: gradient shape {} does not match the output {}".format(
+                self.layer_name, tuple(dy.shape), (N, K, OH, OW)))
+        with weight_grad_stream(dy, x, *self._bn_tensors()):
+            sst = stream_handle()
+            if self.with_bias:
+                gb = grad_buffer(self, "bias", (K,))
+                nb = lib.dk_colsum_workspace_bytes(P, K)
+                lib.dk_colsum_bf16(dy.data_ptr(), P, K, gb.data_ptr(), workspace.get(nb), nb, sst)
+            gw = grad_buffer(self, "weights", (K, C, R, S))
+            s = l2_strength(self.weight_regulariser)
+            nb = lib.dk_conv2d_wgrad_bf16_workspace_bytes(N, OH, OW, K, Cp, R, S)
+            if self._bn_in is not None:
+                lib.dk_conv2d_wgrad_bnx_bf16(dy.data_ptr(), x.data_ptr(), N, H, W, Cp, C, K, R, S, self.stride,
+                                             self.padding, OH, OW, w.data_ptr() if s else 0, s or 0.0, gw.data_ptr(),
+                                             workspace.get(nb), nb, *self._bn_in.bn_args(), sst)
+            else:
+                lib.dk_conv2d_wgrad_bf16(dy.data_ptr(), x.data_ptr(), N, H, W, Cp, C, K, R, S, self.stride,
+                                         self.padding, OH, OW, w.data_ptr() if s else 0, s or 0.0, gw.data_ptr(),
+                                         workspace.get(nb), nb, sst)
+            if s is None:
+                add_regulariser_grad(gw, w, self.weight_regulariser)
+        if not need_dx:
+            return None
+        Hin, Win = self.input_shape[2], self.input_shape[3]
+        dx = empty_nhwc(N, C, Hin, Win, BF16)
+        if self.stride == 1:
+            w_crsk = torch.empty((C, R, S, K), dtype=torch.float32, device=x.device)
+            lib.dk_conv_weight_crsk_f32(w.data_ptr(), K, C, R, S, w_crsk.data_ptr(), st)
+            lib.dk_conv2d_dgrad_bf16(dy.data_ptr(), N, OH, OW, K, w_crsk.data_ptr(), C, R, S, self.padding,
+                                     dx.data_ptr(), Hin, Win, st)
+        else:
+            nb = lib.dk_conv2d_dgrad_phase_workspace_bytes(K, C, R, S, self.stride)
+            lib.dk_conv2d_dgrad_phase_bf16(dy.data_ptr(), N, OH, OW, K, K, w.data_ptr(), C, R, S, self.stride,
+                                           self.padding, dx.data_ptr(), Hin, Win, workspace.get(nb), nb, st)
         return dx
 
     # -- checkpoint hooks (h5py is not available in this image; kept for API parity) ------

@@ -7,7 +7,7 @@ dgrad and wgrad (+ l2) run on the same MFMA GEMM engine as the convolutions
 from __future__ import annotations
 
 from .._hip import lib, stream_handle, weight_grad_stream, workspace
-from .._tensor import ptr, rows
+from .._tensor import BF16, act_dtype, ptr, rows
 from ._common import add_regulariser_grad, grad_buffer, init_weights, l2_strength
 from .layer import Layer
 
@@ -41,8 +41,15 @@ class DenseLayer(Layer):
         return "DenseLayer({}, incoming_chans={}, output_dim={}, weight_regulariser={})".format(
             self.layer_name, self.incoming_chans, self.output_dim, repr(self.weight_regulariser))
 
+    def _refuse_bf16(self, t):
+        # fp32 only: a bf16 tensor would otherwise be read by the _f32 entry points as 4-byte elements
+        if act_dtype(t) == BF16:
+            raise NotImplementedError("DenseLayer {}: no bf16 path (pool a bf16 activation with "
+                                      "GlobalAveragePoolingLayer, whose output is fp32)".format(self.layer_name))
+
     def forward(self, X, test_mode=False):
         self._require_on_gpu()
+        self._refuse_bf16(X)
         st = stream_handle()
         x = rows(X)
         B, IN = x.shape
@@ -57,6 +64,7 @@ class DenseLayer(Layer):
 
     def backward(self, upstream_dx):
         self._require_on_gpu()
+        self._refuse_bf16(upstream_dx)
         st = stream_handle()
         dy = rows(upstream_dx)
         x = self.downstream_X

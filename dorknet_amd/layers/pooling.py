@@ -1,6 +1,8 @@
 """Global average pooling (reference: layers/pooling.py:10-43).
 
 ``forward``: mean over (H, W) -> (N, C); ``backward``: (1/(H*W)) * dy broadcast back.
+A bf16 input (bf16 activation storage) is pooled to fp32 means -- the head after it (DenseLayer,
+the loss) is fp32 -- and its backward returns a bf16 gradient (dk_gap_fwd_bf16 / dk_gap_bwd_bf16).
 (MaxPoolLayer, pooling.py:45-77, is CPU-only in the reference and used by no example:
 out of scope, see DESIGN.md.)
 """
@@ -10,7 +12,7 @@ import torch
 
 from .._env import getenv
 from .._hip import lib, stream_handle
-from .._tensor import empty_nhwc, rows, to_nhwc
+from .._tensor import BF16, empty_nhwc, rows, to_nhwc
 from ._bn_input import JoinOut
 from .layer import Layer
 
@@ -41,13 +43,16 @@ class GlobalAveragePoolingLayer(Layer):
         x = to_nhwc(X)
         N, C, H, W = x.shape
         self.spatial_shape = (H, W)
+        self._in_dtype = x.dtype
         out = torch.empty((N, C), dtype=torch.float32, device=x.device)
-        lib.dk_gap_fwd_f32(x.data_ptr(), N, H * W, C, out.data_ptr(), stream_handle())
+        fwd = lib.dk_gap_fwd_bf16 if x.dtype == BF16 else lib.dk_gap_fwd_f32
+        fwd(x.data_ptr(), N, H * W, C, out.data_ptr(), stream_handle())
         return out
 
     def _forward_join(self, J, test_mode):
         N, C, H, W = J.shape
         self.spatial_shape = (H, W)
+        self._in_dtype = torch.float32
         out = torch.empty((N, C), dtype=torch.float32, device=J.device)
         if not test_mode and J.mask is None:
             # the join's ReLU backward takes its mask (y itself is never stored)
@@ -63,8 +68,9 @@ class GlobalAveragePoolingLayer(Layer):
         dy = rows(upstream_dx)
         N, C = dy.shape
         H, W = self.spatial_shape
-        dx = empty_nhwc(N, C, H, W)
-        lib.dk_gap_bwd_f32(dy.data_ptr(), N, H * W, C, dx.data_ptr(), stream_handle())
+        bf = getattr(self, "_in_dtype", torch.float32) == BF16
+        dx = empty_nhwc(N, C, H, W, BF16 if bf else torch.float32)
+        (lib.dk_gap_bwd_bf16 if bf else lib.dk_gap_bwd_f32)(dy.data_ptr(), N, H * W, C, dx.data_ptr(), stream_handle())
         return dx
 
     def save_to_h5(self, open_f, save_grads=True):

@@ -253,7 +253,10 @@ def work(name: str, args) -> tuple[int, int]:
 # Entry points whose flops run on bf16 MFMA (v_mfma_f32_32x32x16_bf16): their compute roof is the
 # bf16 dense peak; every other entry computes in fp32 (f32 MFMA or VALU, the same 157.3 TF/s).
 BF16_MFMA = {"dk_pwconv_fwd_ex_bf16", "dk_pwconv_dgrad_ex_bf16", "dk_pwconv_wgrad_bnx_bf16",
-             "dk_pwconv_dgrad_bnbwd_bf16"}
+             "dk_pwconv_dgrad_bnbwd_bf16",
+             # the bf16 dense convolution (gemm_bf16.hip)
+             "dk_conv2d_fwd_ex_bf16", "dk_conv2d_dgrad_bf16", "dk_conv2d_dgrad_phase_bf16", "dk_conv2d_wgrad_bf16",
+             "dk_conv2d_wgrad_bnx_bf16"}
 
 
 def peak_tflops(name: str | None = None) -> float:
@@ -281,6 +284,13 @@ def _half(f):
 
 for _n in ("dk_pwconv_fwd_ex", "dk_pwconv_dgrad_ex", "dk_pwconv_wgrad_bnx", "dk_dwconv_fwd_ex", "dk_dwconv_dgrad_ex",
            "dk_dwconv_wgrad_bnx", "dk_bn_stats", "dk_bn_apply", "dk_bn_bwd", "dk_bn_bwd_apply", "dk_relu_fwd",
-           "dk_relu_bwd", "dk_pwconv_dgrad_bnbwd", "dk_dwconv_bwd_bnbwd"):
+           "dk_relu_bwd", "dk_pwconv_dgrad_bnbwd", "dk_dwconv_bwd_bnbwd",
+           # the bf16 dense convolution, its bias gradient and the pooling head
+           "dk_conv2d_fwd_ex", "dk_conv2d_dgrad", "dk_conv2d_dgrad_phase", "dk_conv2d_wgrad", "dk_conv2d_wgrad_bnx",
+           "dk_colsum", "dk_gap_fwd", "dk_gap_bwd"):
     if _n + "_f32" in MODEL:
         MODEL[_n + "_bf16"] = _half(MODEL[_n + "_f32"])
+
+# host-side queries of the bf16 dense convolution: no device work
+for _n in ("dk_conv2d_fwd_bf16_stats_rows", "dk_conv2d_wgrad_bf16_workspace_bytes"):
+    MODEL[_n] = lambda *a: (0, 0)

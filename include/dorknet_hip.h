@@ -268,6 +268,36 @@ int dk_pwconv_dgrad_ex_bf16(const uint16_t* dy, int N, int OH, int OW, int K, co
 int dk_pwconv_wgrad_bnx_bf16(const uint16_t* dy, const uint16_t* x, int N, int H, int W, int C, int K, int stride, int OH, int OW, const float* w_kc, float l2, float* dw_kc, void* ws, size_t ws_bytes, const float* bn_mean, const float* bn_invstd, const float* bn_gamma, const float* bn_beta, int bn_relu, void* stream);
 int dk_dwconv_fwd_ex_bf16(const uint16_t* x, int N, int H, int W, int C, const float* w_crs, int R, int S, int stride, int pad, const float* bias, uint16_t* y, int OH, int OW, const float* bn_mean, const float* bn_invstd, const float* bn_gamma, const float* bn_beta, int bn_relu, double* stats, void* stream);
 int dk_dwconv_dgrad_ex_bf16(const uint16_t* dy, int N, int OH, int OW, int C, const float* w_crs, int R, int S, int stride, int pad, uint16_t* dx, int H, int W, void* ws, size_t ws_bytes, const uint16_t* residual, const uint16_t* bn_x, const float* bn_mean, const float* bn_invstd, const float* bn_gamma, const float* bn_beta, int bn_relu, double* part, void* stream);
+/* Dense convolution with bf16 activations (the twins of dk_conv2d_fwd_ex_f32, dk_conv2d_dgrad_f32,
+ * dk_conv2d_dgrad_phase_f32, dk_conv2d_wgrad_f32 / _bnx_f32; reference layers/convolution.py:58-117):
+ * x, y, dy, dx bf16 NHWC, 8-byte aligned; the weight copies (dk_conv_weight_krsc_f32 / _crsk_f32, or
+ * w_kcrs for the phase dgrad and the weight gradient), bias, BN vectors, statistics and dw_kcrs fp32.
+ * Every GEMM runs on v_mfma_f32_32x32x16_bf16: both operands are rounded to bf16 as they are staged
+ * (the weights; bn(x) under BN on load), products are exact, accumulation is fp32, and the output
+ * is rounded to bf16 once on store.  Padding is exactly 0, also under BN on load.
+ * dk_conv2d_fwd_ex_bf16: any R, S, stride, pad; C % 4 == 0 and K % 4 == 0 (else 10001).  stats: the
+ * output BatchNorm's partial rows [dk_conv2d_fwd_bf16_stats_rows()][2][K], taken over the ROUNDED
+ * stored y (the rule of dk_pwconv_fwd_ex_bf16); takes an in-launch fold arming (dk_bn_fold_arm_stats).
+ * dk_conv2d_dgrad_bf16: stride 1, K % 4 == 0.  dk_conv2d_dgrad_phase_bf16: any stride; dy has
+ * Kp = K rounded up to 4 channels; workspace dk_conv2d_dgrad_phase_workspace_bytes().
+ * dk_conv2d_wgrad_bf16 / _bnx_bf16: x has Cp (% 4 == 0) channels of which the first C are real (the bn_*
+ * vectors hold Cp floats), K % 4 == 0; fp32 split-K slabs and the fixed-order reduce (+ l2 * w_kcrs)
+ * into dw_kcrs[K][C][R][S]; workspace dk_conv2d_wgrad_bf16_workspace_bytes() (its own split rule). */
+int dk_conv2d_fwd_bf16_stats_rows(int N, int OH, int OW, int K, int C, int R, int S);
+int dk_conv2d_fwd_ex_bf16(const uint16_t* x, int N, int H, int W, int C, const float* w_krsc, int K, int R, int S, int stride, int pad, const float* bias, uint16_t* y, int OH, int OW, const float* bn_mean, const float* bn_invstd, const float* bn_gamma, const float* bn_beta, int bn_relu, double* stats, void* stream);
+int dk_conv2d_dgrad_bf16(const uint16_t* dy, int N, int OH, int OW, int K, const float* w_crsk, int C, int R, int S, int pad, uint16_t* dx, int H, int W, void* stream);
+int dk_conv2d_dgrad_phase_bf16(const uint16_t* dy, int N, int OH, int OW, int Kp, int K, const float* w_kcrs, int C, int R, int S, int stride, int pad, uint16_t* dx, int H, int W, void* ws, size_t ws_bytes, void* stream);
+size_t dk_conv2d_wgrad_bf16_workspace_bytes(int N, int OH, int OW, int K, int Cp, int R, int S);
+int dk_conv2d_wgrad_bf16(const uint16_t* dy, const uint16_t* x, int N, int H, int W, int Cp, int C, int K, int R, int S, int stride, int pad, int OH, int OW, const float* w_kcrs, float l2, float* dw_kcrs, void* ws, size_t ws_bytes, void* stream);
+int dk_conv2d_wgrad_bnx_bf16(const uint16_t* dy, const uint16_t* x, int N, int H, int W, int Cp, int C, int K, int R, int S, int stride, int pad, int OH, int OW, const float* w_kcrs, float l2, float* dw_kcrs, void* ws, size_t ws_bytes, const float* bn_mean, const float* bn_invstd, const float* bn_gamma, const float* bn_beta, int bn_relu, void* stream);
+/* The head and the bias gradient with bf16 activations (layers/pooling.py:23-36; convolution.py:91-92):
+ * dk_colsum_bf16: column sums of a bf16 [M][N] matrix, fp64 accumulation in dk_colsum_f32's order,
+ * fp32 result (workspace: dk_colsum_workspace_bytes, the same layout); dk_gap_fwd_bf16: bf16 x -> fp32
+ * [N][C] means; dk_gap_bwd_bf16: fp32 [N][C] dy -> bf16 dx.  The arithmetic is the fp32 twins', widened
+ * on load and rounded once on store. */
+int dk_colsum_bf16(const uint16_t* in, int M, int N, float* out, void* ws, size_t ws_bytes, void* stream);
+int dk_gap_fwd_bf16(const uint16_t* x, int N, int HW, int C, float* out, void* stream);
+int dk_gap_bwd_bf16(const float* dy, int N, int HW, int C, uint16_t* dx, void* stream);
 
 /* BatchNorm-backward-on-load fusions for bf16 storage (as dk_pwconv_dgrad_bnbwd_f32 and
  * dk_dwconv_bwd_bnbwd_f32; reference layers/pointwise_convolution.py:57-75,
@@ -400,7 +430,7 @@ int dk_bn_bwd_from_partials_f32(const void* part, int nblk, int C, double count,
  * exactly what dk_bn_stats_from_partials_f32 (arm_stats) or dk_bn_bwd_from_partials_f32
  * (arm_bwd) would, and the entry point returns DK_FOLDED (10100) instead of 0 -- the caller
  * skips the separate fold launch.  Entry points that take an arming: dk_pwconv_fwd_ex_f32,
- * dk_dwconv_fwd_ex_f32, dk_conv2d_fwd_ex_f32, dk_conv2d_fwd_narrow_f32, dk_pwconv_dgrad_bnbwd_f32, dk_pwconv_dgrad_ex_f32,
+ * dk_dwconv_fwd_ex_f32, dk_conv2d_fwd_ex_f32 / _bf16, dk_conv2d_fwd_narrow_f32, dk_pwconv_dgrad_bnbwd_f32, dk_pwconv_dgrad_ex_f32,
  * dk_pwconv_bwd_bnbwd_f32, dk_dwconv_bwd_bnbwd_f32, dk_dwconv_dgrad_ex_f32,
  * dk_relu_bwd_bn_partial_f64 (for the paths that implement it; otherwise they return 0 and
  * the caller folds as before and calls dk_bn_fold_disarm).  One arming per host thread; the

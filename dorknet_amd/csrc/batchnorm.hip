@@ -879,13 +879,15 @@ DK_API int dk_bn_bwd_partial_f64(const float* x, const float* dy, int P, int C, 
 
 // ReLU backward (mask from the forward join) fused with stage 1 of the backward of the BN
 // that produced the join's input: dx = mask ? dy : 0 and part[nblk][2][C] over dx.
-DK_API int dk_relu_bwd_bn_partial_f64(const float* dy, const uint8_t* mask, const float* x, int P, int C,
-                                      const float* mean, const float* invstd, const float* gamma, const float* beta,
-                                      int relu, float* dx, void* part, size_t part_bytes, void* stream) {
+template <class E>
+static int relu_bwd_bn_partial_t(const E* dy, const uint8_t* mask, const E* x, int P, int C, const float* mean,
+                                 const float* invstd, const float* gamma, const float* beta, int relu, E* dx,
+                                 void* part, size_t part_bytes, void* stream) {
   if (part_bytes < dk_bn_workspace_bytes(P, C)) return DK_ERR_WORKSPACE;
   const int nblk = bn_blocks(P, C);
   const int ppb = cdiv(P, nblk);
-  const bool vec = vec_ok(x, C) && vec_ok(dy, C) && vec_ok(dx, C) && (reinterpret_cast<uintptr_t>(mask) & 3) == 0;
+  const bool vec = vec_ok_e(x, C) && vec_ok_e(dy, C) && vec_ok_e(dx, C) && (reinterpret_cast<uintptr_t>(mask) & 3) == 0;
+  if (!vec && sizeof(E) != 4) return DK_ERR_ARGS;
   // the same partial rows (pixel ranges) as the other BN passes, but at most 32 channel groups per block:
   // the head's 7 x 7 x 512 join (P = 12,544) otherwise ran 196 blocks of 2 pixel lanes, one per CU
   // on 196 CUs, each lane walking 32 pixels
@@ -895,12 +897,25 @@ DK_API int dk_relu_bwd_bn_partial_f64(const float* dy, const uint8_t* mask, cons
   FoldTail ft;  // an armed in-launch fold of the partial rows (fold_tail.h)
   if (!fold_take(part, nblk, C, (int)grid.y, &ft) || ((g.cgt * (vec ? 4 : 1)) & 1)) ft.part = nullptr;
   if (vec)
-    hipLaunchKernelGGL((bn_bwd_partial_kernel<4, true>), grid, dim3(256), 0, as_stream(stream), x, dy, P, C, ppb,
+    hipLaunchKernelGGL((bn_bwd_partial_kernel<4, true, E>), grid, dim3(256), 0, as_stream(stream), x, dy, P, C, ppb,
                        mean, invstd, gamma, beta, relu, static_cast<double*>(part), mask, dx, ft, cap);
   else
-    hipLaunchKernelGGL((bn_bwd_partial_kernel<1, true>), grid, dim3(256), 0, as_stream(stream), x, dy, P, C, ppb,
+    hipLaunchKernelGGL((bn_bwd_partial_kernel<1, true, E>), grid, dim3(256), 0, as_stream(stream), x, dy, P, C, ppb,
                        mean, invstd, gamma, beta, relu, static_cast<double*>(part), mask, dx, ft, cap);
   return fold_status(launch_status(), ft);
+}
+DK_API int dk_relu_bwd_bn_partial_f64(const float* dy, const uint8_t* mask, const float* x, int P, int C,
+                                      const float* mean, const float* invstd, const float* gamma, const float* beta,
+                                      int relu, float* dx, void* part, size_t part_bytes, void* stream) {
+  return relu_bwd_bn_partial_t(dy, mask, x, P, C, mean, invstd, gamma, beta, relu, dx, part, part_bytes, stream);
+}
+// The same for bf16 storage (dy, x, dx bf16; C % 4 == 0): dx = mask ? dy : 0 is exact, the sums are
+// the fp32 entry's over the widened values, in the same rows.
+DK_API int dk_relu_bwd_bn_partial_bf16(const bf16_t* dy, const uint8_t* mask, const bf16_t* x, int P, int C,
+                                       const float* mean, const float* invstd, const float* gamma, const float* beta,
+                                       int relu, bf16_t* dx, void* part, size_t part_bytes, void* stream) {
+  if (!dy || !mask || !x || !dx || P < 1 || C < 4 || C % 4) return DK_ERR_ARGS;
+  return relu_bwd_bn_partial_t(dy, mask, x, P, C, mean, invstd, gamma, beta, relu, dx, part, part_bytes, stream);
 }
 
 // Backward stage 2 from partials of any origin (dk_bn_bwd_partial_f64, a consumer's

@@ -59,8 +59,10 @@ __global__ void mask_to_f32_kernel(const uint8_t* __restrict__ mask, long long n
 }
 
 // y = a + b, optionally ReLU'd with mask.
-__global__ __launch_bounds__(256) void add_kernel(const float* __restrict__ a, const float* __restrict__ b,
-                                                  long long n, int relu, float* __restrict__ y,
+// (E: activation storage -- float, or bf16_t widened on load, the fp32 sum rounded once on store)
+template <class E = float>
+__global__ __launch_bounds__(256) void add_kernel(const E* __restrict__ a, const E* __restrict__ b,
+                                                  long long n, int relu, E* __restrict__ y,
                                                   uint8_t* __restrict__ mask, int vec) {
   const long long nv = vec ? (n >> 2) : 0;
   const long long stride = (long long)gridDim.x * blockDim.x;
@@ -79,13 +81,13 @@ __global__ __launch_bounds__(256) void add_kernel(const float* __restrict__ a, c
     st4(y + 4 * i, v);
   }
   for (long long i = 4 * nv + (long long)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += stride) {
-    float v = a[i] + b[i];
+    float v = ld1(a + i) + ld1(b + i);
     if (relu) {
       const bool pos = v > 0.f;
       v = pos ? v : 0.f;
       if (mask) mask[i] = pos;
     }
-    y[i] = v;
+    st1(y + i, v);
   }
 }
 
@@ -97,28 +99,73 @@ __device__ __forceinline__ f32x4 bn_in4_at(f32x4 v, const BnIn& bn, int c) {
   return bn_in4(v, ld4(bn.mean + c), ld4(bn.invstd + c), ld4(bn.gamma + c), ld4(bn.beta + c), bn.relu);
 }
 
-__global__ __launch_bounds__(256) void bn_add_kernel(const float* __restrict__ a, BnIn ba, const float* __restrict__ b,
-                                                     BnIn bb, long long n, int C, int relu, float* __restrict__ y,
+// V consecutive elements as V / 4 fp32 quads.  V = 8 is bf16 only: one 16-byte access.
+template <int V, class E>
+__device__ __forceinline__ void ldv(const E* p, f32x4* q) {
+  if constexpr (V == 4) {
+    q[0] = ld4(p);
+  } else {
+    static_assert(V == 8 && sizeof(E) == 2, "16-byte chunks: 8 bf16");
+    const uint4 u = *reinterpret_cast<const uint4*>(p);
+    q[0] = bf16x4_to_f32(uint2{u.x, u.y});
+    q[1] = bf16x4_to_f32(uint2{u.z, u.w});
+  }
+}
+template <int V, class E>
+__device__ __forceinline__ void stv(E* p, const f32x4* q, int nt) {
+  if constexpr (V == 4) {
+    if (nt)
+      st4nt(p, q[0]);
+    else
+      st4(p, q[0]);
+  } else {
+    static_assert(V == 8 && sizeof(E) == 2, "16-byte chunks: 8 bf16");
+    typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
+    const uint2 lo = f32_to_bf16x4(q[0]), hi = f32_to_bf16x4(q[1]);
+    const u32x4 u = {lo.x, lo.y, hi.x, hi.y};
+    if (nt)
+      __builtin_nontemporal_store(u, reinterpret_cast<u32x4*>(p));
+    else
+      *reinterpret_cast<u32x4*>(p) = u;
+  }
+}
+
+// (E: activation storage of a, b and y -- float, or bf16_t: widened on load, the same fp32 operations in
+// the same order, the mask taken from the fp32 value, one rounding on store.  V: elements per thread and
+// pass, 4, or 8 for bf16 with C % 8 == 0 -- 16-byte accesses, the mask as one 8-byte word)
+template <class E = float, int V = 4>
+__global__ __launch_bounds__(256) void bn_add_kernel(const E* __restrict__ a, BnIn ba, const E* __restrict__ b,
+                                                     BnIn bb, long long n, int C, int relu, E* __restrict__ y,
                                                      uint8_t* __restrict__ mask, int nt) {
-  const long long nv = n >> 2;
+  constexpr int Q = V / 4;
+  const long long nv = n / V;
   const long long stride = (long long)gridDim.x * blockDim.x;
   for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < nv; i += stride) {
-    const int c = (int)((uint32_t)(4 * i) % (uint32_t)C);
-    f32x4 v = bn_in4_at(ld4(a + 4 * i), ba, c) + bn_in4_at(ld4(b + 4 * i), bb, c);
-    if (relu) {
-      uint32_t m = 0;
+    const int c = (int)((uint32_t)(V * i) % (uint32_t)C);
+    f32x4 va[Q], vb[Q], v[Q];
+    ldv<V>(a + V * i, va);
+    ldv<V>(b + V * i, vb);
+    uint32_t m[Q];
 #pragma unroll
-      for (int e = 0; e < 4; ++e) {
-        const bool pos = v[e] > 0.f;
-        v[e] = pos ? v[e] : 0.f;
-        m |= (uint32_t)pos << (8 * e);
+    for (int q = 0; q < Q; ++q) {
+      v[q] = bn_in4_at(va[q], ba, c + 4 * q) + bn_in4_at(vb[q], bb, c + 4 * q);
+      m[q] = 0;
+      if (relu) {
+#pragma unroll
+        for (int e = 0; e < 4; ++e) {
+          const bool pos = v[q][e] > 0.f;
+          v[q][e] = pos ? v[q][e] : 0.f;
+          m[q] |= (uint32_t)pos << (8 * e);
+        }
       }
-      if (mask) reinterpret_cast<uint32_t*>(mask)[i] = m;
     }
-    if (nt)
-      st4nt(y + 4 * i, v);
-    else
-      st4(y + 4 * i, v);
+    if (relu && mask) {
+      if constexpr (Q == 1)
+        reinterpret_cast<uint32_t*>(mask)[i] = m[0];
+      else
+        reinterpret_cast<uint2*>(mask)[i] = uint2{m[0], m[1]};
+    }
+    stv<V>(y + V * i, v, nt);
   }
 }
 
@@ -586,9 +633,21 @@ DK_API int dk_mask_to_f32(const uint8_t* mask, long long n, float* out, void* st
 }
 
 DK_API int dk_add_f32(const float* a, const float* b, long long n, int relu, float* y, uint8_t* mask, void* stream) {
-  hipLaunchKernelGGL(add_kernel, grid4(n), dim3(256), 0, as_stream(stream), a, b, n, relu, y, mask,
+  hipLaunchKernelGGL(add_kernel<float>, grid4(n), dim3(256), 0, as_stream(stream), a, b, n, relu, y, mask,
                      (int)(al16(a) && al16(b) && al16(y) && al4(mask)));
   return launch_status();
+}
+
+// bf16 storage: a, b, y bf16 (8-byte aligned), the fp32 sum of the widened operands rounded once on store
+DK_API int dk_add_bf16(const bf16_t* a, const bf16_t* b, long long n, int relu, bf16_t* y, uint8_t* mask,
+                       void* stream) {
+  if (!a || !b || !y || n < 1 || !al8(a) || !al8(b) || !al8(y) || !al4(mask)) return DK_ERR_ARGS;
+  hipLaunchKernelGGL(add_kernel<bf16_t>, grid4(n), dim3(256), 0, as_stream(stream), a, b, n, relu, y, mask, 1);
+  return launch_status();
+}
+
+static inline bool bn_add_params_ok(const BnIn& p) {
+  return !p.mean || (p.invstd && p.gamma && p.beta && al16(p.mean) && al16(p.invstd) && al16(p.gamma) && al16(p.beta));
 }
 
 DK_API int dk_bn_add_f32(const float* a, const float* a_mean, const float* a_invstd, const float* a_gamma,
@@ -596,14 +655,35 @@ DK_API int dk_bn_add_f32(const float* a, const float* a_mean, const float* a_inv
                          const float* b_gamma, const float* b_beta, int b_relu, long long n, int C, int relu, float* y,
                          uint8_t* mask, void* stream) {
   const BnIn ba{a_mean, a_invstd, a_gamma, a_beta, a_relu}, bb{b_mean, b_invstd, b_gamma, b_beta, b_relu};
-  auto params_ok = [](const BnIn& p) {
-    return !p.mean || (p.invstd && p.gamma && p.beta && al16(p.mean) && al16(p.invstd) && al16(p.gamma) &&
-                       al16(p.beta));
-  };
-  if (C < 4 || C % 4 || n % C || n >= (1ll << 31) || !al16(a) || !al16(b) || !al16(y) || !al4(mask) || !params_ok(ba) || !params_ok(bb))
+  if (C < 4 || C % 4 || n % C || n >= (1ll << 31) || !al16(a) || !al16(b) || !al16(y) || !al4(mask) ||
+      !bn_add_params_ok(ba) || !bn_add_params_ok(bb))
     return DK_ERR_ARGS;
-  hipLaunchKernelGGL(bn_add_kernel, grid4(n), dim3(256), 0, as_stream(stream), a, ba, b, bb, n, C, relu, y, mask,
-                     nt_stores(kNtBnAdd));
+  hipLaunchKernelGGL((bn_add_kernel<float, 4>), grid4(n), dim3(256), 0, as_stream(stream), a, ba, b, bb, n, C, relu, y,
+                     mask, nt_stores(kNtBnAdd));
+  return launch_status();
+}
+
+// dk_bn_add_f32 for bf16 storage (a, b, y bf16; BN parameters fp32): bit-identical to widening both
+// operands, dk_bn_add_f32, and rounding y to bf16; the mask is the fp32 entry's (v > 0 before rounding).
+// 16-byte accesses (8 channels) when C % 8 == 0 and the pointers allow, else 8-byte (4 channels).
+DK_API int dk_bn_add_bf16(const bf16_t* a, const float* a_mean, const float* a_invstd, const float* a_gamma,
+                          const float* a_beta, int a_relu, const bf16_t* b, const float* b_mean,
+                          const float* b_invstd, const float* b_gamma, const float* b_beta, int b_relu, long long n,
+                          int C, int relu, bf16_t* y, uint8_t* mask, void* stream) {
+  const BnIn ba{a_mean, a_invstd, a_gamma, a_beta, a_relu}, bb{b_mean, b_invstd, b_gamma, b_beta, b_relu};
+  if (!a || !b || !y || n < 1 || C < 4 || C % 4 || n % C || n >= (1ll << 31) || !al8(a) || !al8(b) || !al8(y) ||
+      !al4(mask) || !bn_add_params_ok(ba) || !bn_add_params_ok(bb))
+    return DK_ERR_ARGS;
+  const int nt = nt_stores(kNtBnAdd);
+  if (C % 8 == 0 && al16(a) && al16(b) && al16(y) && al8(mask)) {
+    long long blocks = cdivll(n / 8, 256);
+    blocks = blocks > 16384 ? 16384 : (blocks < 1 ? 1 : blocks);
+    hipLaunchKernelGGL((bn_add_kernel<bf16_t, 8>), dim3((unsigned)blocks), dim3(256), 0, as_stream(stream), a, ba, b,
+                       bb, n, C, relu, y, mask, nt);
+  } else {
+    hipLaunchKernelGGL((bn_add_kernel<bf16_t, 4>), grid4(n), dim3(256), 0, as_stream(stream), a, ba, b, bb, n, C, relu,
+                       y, mask, nt);
+  }
   return launch_status();
 }
 

@@ -80,31 +80,58 @@ DK_API int dk_pwconv_fwd_ex_bf16(const bf16_t* x, int N, int H, int W, int C, co
   return run(a);
 }
 
-// Stride-1 pointwise dgrad (bf16): dx = dy . W (+ residual) and, with bn_x/part, the
-// BN-backward partials of the BatchNorm whose output the layer consumed.
+// partial rows of dk_pwconv_dgrad_ex_bf16 (any stride): one per M tile of the tiled engine, the tile
+// chosen by the row_config call of the launch below (M x C output, reduction K, plain loaders, bf16 MFMA)
+DK_API int dk_pwconv_dgrad_bf16_stats_rows(int N, int OH, int OW, int K, int C, int stride) {
+  (void)stride;  // the GEMM is over the N x OH x OW lattice at every stride
+  return stats_rows(N * OH * OW, C, K, kRowPlain, kMfBf16);
+}
+
+// Pointwise dgrad (bf16): dx = dy . W (+ residual) and, with bn_x/part, the BN-backward partials of
+// the BatchNorm whose output the layer consumed.  stride > 1: dx is the widened (OH*stride) x
+// (OW*stride) grid, zeros off the sampling lattice (dk_pwconv_dgrad_ex_f32's rules: a residual on
+// the widened grid only without part; bn_x on the widened grid).
 DK_API int dk_pwconv_dgrad_ex_bf16(const bf16_t* dy, int N, int OH, int OW, int K, const float* w_kc, int C,
                                    int stride, bf16_t* dx, const bf16_t* residual, const bf16_t* bn_x,
                                    const float* bn_mean, const float* bn_invstd, const float* bn_gamma,
                                    const float* bn_beta, int bn_relu, double* part, void* stream) {
+  if (N < 1 || OH < 1 || OW < 1 || K < 4 || C < 4 || stride < 1 || stride > 8) return DK_ERR_ARGS;
+  if ((long long)N * OH * OW >= (1ll << 31)) return DK_ERR_ARGS;
   const int M = N * OH * OW;
-  if (stride != 1 || C % 4 || K % 4 || !al8(dy) || !al8(dx) || !aligned16(w_kc)) return DK_ERR_ARGS;
+  if (C % 4 || K % 4 || !dy || !dx || !al8(dy) || !al8(dx) || !aligned16(w_kc)) return DK_ERR_ARGS;
   if ((residual && !al8(residual)) || (bn_x && !al8(bn_x))) return DK_ERR_ARGS;
-  if (!fits((size_t)M * K * 4) || !fits((size_t)M * C * 4) || (part != nullptr) != (bn_x != nullptr)) return DK_ERR_ARGS;
+  if (!fits((size_t)M * K * 4) || !fits((size_t)M * C * 4 * stride * stride) || (part != nullptr) != (bn_x != nullptr))
+    return DK_ERR_ARGS;
+  if (part && residual && stride != 1) return DK_ERR_ARGS;  // off-lattice residual terms would need reducing
   const MatDescE<bf16_t> a = mat_h(dy, M, K, M);
   const MatDesc b = mat(w_kc, K, C, C);
   const hipStream_t st = as_stream(stream);
   if (!part) {
-    EpStoreT<bf16_t> ep{dx, C, nullptr, 1, residual};
-    return igemm_rows<LdMatKC, MatDescE<bf16_t>, LdMatIC, MatDesc, EpStoreT<bf16_t>, kRowPlain, kMfBf16>(a, b, ep, M, C,
+    if (stride == 1) {
+      EpStoreT<bf16_t> ep{dx, C, nullptr, 1, residual};
+      return igemm_rows<LdMatKC, MatDescE<bf16_t>, LdMatIC, MatDesc, EpStoreT<bf16_t>, kRowPlain, kMfBf16>(a, b, ep, M,
+                                                                                                             C, K, st);
+    }
+    EpWidenT<bf16_t> ep{dx, C, OH, OW, stride, 1, residual};
+    return igemm_rows<LdMatKC, MatDescE<bf16_t>, LdMatIC, MatDesc, EpWidenT<bf16_t>, kRowPlain, kMfBf16>(a, b, ep, M, C,
                                                                                                            K, st);
   }
   if (!bn_ok(bn_mean, bn_invstd, bn_gamma, bn_beta)) return DK_ERR_ARGS;
-  EpStoreBnBwdT<bf16_t> ep{};
-  ep.out = dx, ep.ldo = C, ep.bias = nullptr, ep.v4 = 1, ep.res = residual;
+  if (stride == 1) {
+    EpStoreBnBwdT<bf16_t> ep{};
+    ep.out = dx, ep.ldo = C, ep.bias = nullptr, ep.v4 = 1, ep.res = residual;
+    ep.part = part;
+    ep.xbn = bn_x;
+    ep.bn = BnIn{bn_mean, bn_invstd, bn_gamma, bn_beta, bn_relu};
+    return igemm_rows<LdMatKC, MatDescE<bf16_t>, LdMatIC, MatDesc, EpStoreBnBwdT<bf16_t>, kRowPlain, kMfBf16>(
+        a, b, ep, M, C, K, st);
+  }
+  EpWidenBnBwdT<bf16_t> ep{};
+  ep.out = dx, ep.ldo = C, ep.OH = OH, ep.OW = OW, ep.st = stride, ep.v4 = 1, ep.res = nullptr;
   ep.part = part;
   ep.xbn = bn_x;
   ep.bn = BnIn{bn_mean, bn_invstd, bn_gamma, bn_beta, bn_relu};
-  return igemm_rows<LdMatKC, MatDescE<bf16_t>, LdMatIC, MatDesc, EpStoreBnBwdT<bf16_t>, kRowPlain, kMfBf16>(
+  return igemm_rows<LdMatKC, MatDescE<bf16_t>, LdMatIC, MatDesc, EpWidenBnBwdT<bf16_t>, kRowPlain, kMfBf16>(
       a, b, ep, M, C, K, st);
 }
 

@@ -668,13 +668,16 @@ using EpStoreBnBwd = EpStoreBnBwdT<float>;
 // Pointwise stride-st backward "widen" (pointwise_convolution.py:68-72) fused: the GEMM
 // row m = (b, oh, ow) of an OH x OW grid lands at (b, oh*st, ow*st) of an
 // (OH*st) x (OW*st) grid and the other st*st-1 positions of that cell are zero.
-struct EpWiden {
+// O: output element type (float, or bf16_t: lattice values, and lattice + residual sums, rounded once
+// on store; the off-lattice zeros and residual copies are exact).
+template <class O>
+struct EpWidenT {
   static constexpr bool kColStats = false;
-  float* out;
+  O* out;
   int ldo;
   int OH, OW, st;
   int v4;
-  const float* res;  // optional residual addend on the widened grid (off-lattice: out = res)
+  const O* res;  // optional residual addend on the widened grid (off-lattice: out = res)
   __device__ __forceinline__ size_t cell(int m) const {
     const int ow = m % OW;
     const int t = m / OW;
@@ -703,29 +706,37 @@ struct EpWiden {
     for (int dy = 0; dy < st; ++dy)
       for (int dx = 0; dx < st; ++dx) {
         const size_t o = (c0 + dy * W2 + dx) * ldo + n;
-        out[o] = ((dy | dx) ? 0.f : v) + (res ? res[o] : 0.f);
+        st1(out + o, ((dy | dx) ? 0.f : v) + (res ? ld1(res + o) : 0.f));
       }
   }
 };
+using EpWiden = EpWidenT<float>;
 
 // EpWiden + the BN-backward reduction over the written (lattice) points; the zeros off the
-// lattice contribute nothing.
-struct EpWidenBnBwd : EpWiden {
+// lattice contribute nothing.  (bf16: the sums are taken over the stored, rounded values --
+// EpStoreBnBwdT<bf16_t>'s rule -- so the BatchNorm's backward sees the gradient its consumers read.)
+template <class O>
+struct EpWidenBnBwdT : EpWidenT<O> {
   static constexpr bool kColStats = true;
+  using Pre = typename EpWidenT<O>::Pre;
   double* part;
   FoldTail ft{};
-  const float* xbn;  // the BN's raw input on the widened grid
+  const O* xbn;  // the BN's raw input on the widened grid
   BnIn bn;
-  __device__ __forceinline__ Pre pre4(int m, int n) const { return Pre{ld4(xbn + cell(m) * ldo + n)}; }
+  __device__ __forceinline__ Pre pre4(int m, int n) const { return Pre{ld4(xbn + this->cell(m) * this->ldo + n)}; }
   __device__ __forceinline__ void put4(int m, int n, f32x4 v, const Pre& p, int sp, double* a, double* b) const {
-    EpWiden::put4(m, n, v, p, sp, a, b);
+    v = rnd4<O>(v);
+    EpWidenT<O>::put4(m, n, v, p, sp, a, b);
     bn_bwd_contrib4(v, p.x, bn, n, a, b);
   }
   __device__ __forceinline__ void put1(int m, int n, float v, int sp, double& a, double& b) const {
-    EpWiden::put1(m, n, v, sp, a, b);
-    bn_bwd_contrib(v, xbn[cell(m) * ldo + n], bn.mean[n], bn.invstd[n], bn.gamma[n], bn.beta[n], bn.relu, a, b);
+    v = rnd1<O>(v);
+    EpWidenT<O>::put1(m, n, v, sp, a, b);
+    bn_bwd_contrib(v, ld1(xbn + this->cell(m) * this->ldo + n), bn.mean[n], bn.invstd[n], bn.gamma[n], bn.beta[n],
+                   bn.relu, a, b);
   }
 };
+using EpWidenBnBwd = EpWidenBnBwdT<float>;
 
 // EpWidenBnBwd with the widened gradient kept compact: only the lattice points are stored, as
 // the OH x OW grid out[m][n]; the BN-backward sums read the BN's input at the lattice points of

@@ -21,7 +21,7 @@ from __future__ import annotations
 import torch
 
 from .._hip import DK_FOLDED, inlaunch_folds_enabled, lib, stream_handle
-from .._tensor import empty_nhwc, is_nhwc, to_nhwc
+from .._tensor import act_dtype, empty_nhwc, is_nhwc, to_nhwc
 
 
 class BNOut:
@@ -299,10 +299,14 @@ def residual_operand(residual, like):
 
 def add_residual(dx, residual):
     """dx + residual (the unfused residual join, residual_block.py:94-97)."""
+    if act_dtype(dx) != act_dtype(residual):
+        raise ValueError("residual backward of mixed storage types: {} vs {}".format(act_dtype(dx),
+                                                                                     act_dtype(residual)))
     a = to_nhwc(dx)
     b = to_nhwc(dense_residual(residual, a.shape))
     if a.shape != b.shape:
         raise ValueError("residual backward shape mismatch: {} vs {}".format(tuple(a.shape), tuple(b.shape)))
-    out = empty_nhwc(*a.shape)
-    lib.dk_add_f32(a.data_ptr(), b.data_ptr(), a.numel(), 0, out.data_ptr(), 0, stream_handle())
+    add = lib.dk_add_bf16 if a.dtype == torch.bfloat16 else lib.dk_add_f32
+    out = empty_nhwc(*a.shape, dtype=a.dtype)
+    add(a.data_ptr(), b.data_ptr(), a.numel(), 0, out.data_ptr(), 0, stream_handle())
     return out

@@ -21,6 +21,13 @@ def _same_layout(X):
     return to_nhwc(X) if X.dim() == 4 else rows(X)
 
 
+def _bf16(*ts):
+    """Whether the operands are bf16 storage (the _bf16 entries); mixed storage types are refused."""
+    if len({t.dtype for t in ts}) != 1:
+        raise ValueError("operands of mixed storage types: {}".format(", ".join(str(t.dtype) for t in ts)))
+    return ts[0].dtype == torch.bfloat16
+
+
 class ReLu(Layer):
 
     def __init__(self, layer_name):
@@ -67,6 +74,8 @@ class ReLu(Layer):
         defer: the consumer of the result can form it on load (ResidualBlock.takes_join_input):
         return a JoinOut (layers/_bn_input.py) instead of running the join pass."""
         self._require_on_gpu()
+        if act_dtype(A) != act_dtype(B):
+            raise ValueError("residual join of mixed storage types: {} vs {}".format(act_dtype(A), act_dtype(B)))
         st = stream_handle()
         if isinstance(A, JoinOut):
             A = A.materialize()
@@ -81,13 +90,13 @@ class ReLu(Layer):
         a, b = _same_layout(A), _same_layout(B)
         if a.shape != b.shape:
             raise ValueError("residual join shape mismatch: {} vs {}".format(tuple(a.shape), tuple(b.shape)))
+        add = lib.dk_add_bf16 if _bf16(a, b) else lib.dk_add_f32
         y = self._empty_like(a)
         mask = None
         if not test_mode:
             mask = torch.empty(a.shape, dtype=torch.uint8, device=a.device,
                                memory_format=torch.channels_last if a.dim() == 4 else torch.contiguous_format)
-        lib.dk_add_f32(a.data_ptr(), b.data_ptr(), a.numel(), 1, y.data_ptr(),
-                       0 if mask is None else mask.data_ptr(), st)
+        add(a.data_ptr(), b.data_ptr(), a.numel(), 1, y.data_ptr(), 0 if mask is None else mask.data_ptr(), st)
         if not test_mode:
             self._mask, self._fused_out, self._join_bn = mask, None, None
             self._join_y = None
@@ -120,12 +129,13 @@ class ReLu(Layer):
         (a, pa), (b, pb) = parts(A), parts(B)
         if not (is_nhwc_t(a) and is_nhwc_t(b)):
             return None
-        y = empty_nhwc(*a.shape)
+        bn_add = lib.dk_bn_add_bf16 if _bf16(a, b) else lib.dk_bn_add_f32
+        y = empty_nhwc(*a.shape, dtype=a.dtype)
         mask = None
         if not test_mode:
             mask = torch.empty(a.shape, dtype=torch.uint8, device=a.device, memory_format=torch.channels_last)
-        lib.dk_bn_add_f32(a.data_ptr(), *pa, b.data_ptr(), *pb, a.numel(), a.shape[1], 1, y.data_ptr(),
-                          0 if mask is None else mask.data_ptr(), st)
+        bn_add(a.data_ptr(), *pa, b.data_ptr(), *pb, a.numel(), a.shape[1], 1, y.data_ptr(),
+               0 if mask is None else mask.data_ptr(), st)
         if not test_mode:
             self._mask, self._fused_out = mask, None
             self._join_bn = A if isinstance(A, BNOut) else None
@@ -144,7 +154,8 @@ class ReLu(Layer):
         when the join left none (a JoinOut whose consumer takes it as y > 0)."""
         y = self._join_y
         mask = torch.empty(y.shape, dtype=torch.uint8, device=y.device, memory_format=torch.channels_last)
-        lib.dk_relu_fwd_f32(y.data_ptr(), y.numel(), 0, mask.data_ptr(), stream_handle())  # mask-only pass
+        fwd = lib.dk_relu_fwd_bf16 if y.dtype == torch.bfloat16 else lib.dk_relu_fwd_f32
+        fwd(y.data_ptr(), y.numel(), 0, mask.data_ptr(), stream_handle())  # mask-only pass
         self._mask, self._join_y = mask, None
         return mask
 
@@ -162,8 +173,10 @@ class ReLu(Layer):
             y = as_device(self._fused_out)  # a BNOut is materialised here
             mask = torch.empty(y.shape, dtype=torch.uint8, device=y.device,
                                memory_format=torch.channels_last if y.dim() == 4 else torch.contiguous_format)
-            lib.dk_relu_fwd_f32(y.data_ptr(), y.numel(), 0, mask.data_ptr(), stream_handle())  # mask-only pass
-            out = self._empty_like(y)
+            fwd = lib.dk_relu_fwd_bf16 if y.dtype == torch.bfloat16 else lib.dk_relu_fwd_f32
+            fwd(y.data_ptr(), y.numel(), 0, mask.data_ptr(), stream_handle())  # mask-only pass
+            out = torch.empty(y.shape, dtype=torch.float32, device=y.device,
+                              memory_format=torch.channels_last if y.dim() == 4 else torch.contiguous_format)
             lib.dk_mask_to_f32(mask.data_ptr(), mask.numel(), out.data_ptr(), stream_handle())
             return out
         return None
@@ -189,8 +202,9 @@ class ReLu(Layer):
             nb = lib.dk_bn_workspace_bytes(P, C)
             part = torch.empty((lib.dk_bn_partial_blocks(P, C), 2, C), dtype=torch.float64, device=dy.device)
             tok = bn.arm_partials(part)
-            r = lib.dk_relu_bwd_bn_partial_f64(dy.data_ptr(), self._mask.data_ptr(), bn.x.data_ptr(), P, C,
-                                               *bn.bn_args(), dx.data_ptr(), part.data_ptr(), nb, stream_handle())
+            bwd = lib.dk_relu_bwd_bn_partial_bf16 if _bf16(dy, bn.x) else lib.dk_relu_bwd_bn_partial_f64
+            r = bwd(dy.data_ptr(), self._mask.data_ptr(), bn.x.data_ptr(), P, C, *bn.bn_args(), dx.data_ptr(),
+                    part.data_ptr(), nb, stream_handle())
             bn.hand_backward_partials(dx, part, r, tok)
             return dx
         bwd = lib.dk_relu_bwd_bf16 if dy.dtype == torch.bfloat16 else lib.dk_relu_bwd_f32

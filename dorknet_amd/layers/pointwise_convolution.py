@@ -170,8 +170,11 @@ class PointwiseConvLayer(Layer):
         `_dk_lattice = s`) when lattice_ok(); chain_backward asks for it only when the consumer of
         that gradient takes the lattice form."""
         self._require_on_gpu()
-        st = stream_handle()
         x = self.X
+        if x.dtype == BF16 and self.with_bias:
+            raise NotImplementedError("{}: bf16 storage has no bias gradient (with_bias=False)".format(
+                self.layer_name))
+        st = stream_handle()
         N, C, H, W = x.shape
         K, s = self.num_filters, self.stride
         OH, OW = self.out_hw
@@ -196,9 +199,8 @@ class PointwiseConvLayer(Layer):
         bf = x.dtype == BF16
         if C != self.num_channels:
             return self._backward_padded(dy, residual, need_dx, st)
-        if bf and (dy.dtype != BF16 or self.with_bias or s != 1):
-            raise NotImplementedError("{}: bf16 storage needs a bf16 gradient, no bias, stride 1".format(
-                self.layer_name))
+        if bf and dy.dtype != BF16:
+            raise NotImplementedError("{}: bf16 storage needs a bf16 gradient".format(self.layer_name))
         self._wgrad(dy, x, N, H, W, C, K, s, OH, OW, P, w, bf)
         if need_dx and lattice_out and residual is None and not bf and self.lattice_ok():
             return self._dgrad_lattice(dy, st)
@@ -451,18 +453,23 @@ class PointwiseConvLayer(Layer):
         bn = self._bn_in
         res = residual_operand(residual, dx)
         if bf:
-            if residual is not None and res is None:
-                raise NotImplementedError("{}: bf16 residual must be a bf16 NHWC tensor".format(self.layer_name))
-            if bn is not None and (OH, OW) == (H, W):
-                rows = lib.dk_pwconv_dgrad_stats_rows(N, OH, OW, K, C)
+            # the input BatchNorm's partials ride on the dgrad when its grid is the (widened) dx grid; a
+            # residual goes in the epilogue except beside partials at stride > 1 (the entry refuses that
+            # pair: off-lattice residual terms would need reducing), where it is added afterwards
+            with_part = bn is not None and (OH * s, OW * s) == (H, W)
+            fused = res if (s == 1 or not with_part) else None
+            if with_part:
+                rows = lib.dk_pwconv_dgrad_bf16_stats_rows(N, OH, OW, K, C, s)
                 part = torch.empty((rows, 2, C), dtype=torch.float64, device=dx.device)
                 tok = bn.arm_partials(part)
                 r = lib.dk_pwconv_dgrad_ex_bf16(dy.data_ptr(), N, OH, OW, K, w.data_ptr(), C, s, dx.data_ptr(),
-                                                ptr(res), bn.x.data_ptr(), *bn.bn_args(), part.data_ptr(), st)
+                                                ptr(fused), bn.x.data_ptr(), *bn.bn_args(), part.data_ptr(), st)
                 bn.hand_backward_partials(dx, part, r, tok)
             else:
-                lib.dk_pwconv_dgrad_ex_bf16(dy.data_ptr(), N, OH, OW, K, w.data_ptr(), C, s, dx.data_ptr(), ptr(res),
+                lib.dk_pwconv_dgrad_ex_bf16(dy.data_ptr(), N, OH, OW, K, w.data_ptr(), C, s, dx.data_ptr(), ptr(fused),
                                             0, 0, 0, 0, 0, 0, 0, st)
+            if residual is not None and fused is None:
+                dx = add_residual(dx, residual)  # (a new tensor: the BN then recomputes its sums)
             return dx
         if bn is not None and (OH * s, OW * s) == (H, W) and (res is None or s == 1):
             # + stage 1 of the input BatchNorm's backward, in the dgrad epilogue

@@ -13,7 +13,7 @@ from __future__ import annotations
 
 from .._env import enabled, getenv
 from .._hip import branch_stream_enabled, lib, on_branch, resolve, stream_handle
-from .._tensor import empty_nhwc, to_nhwc
+from .._tensor import BF16, act_dtype, empty_nhwc, to_nhwc
 from ._bn_input import JoinOut, accepts_bn_input, materialize
 from ._chain import chain_backward, chain_forward, execute, fusion_enabled, notify_backward_done
 from .activations import ReLu
@@ -25,11 +25,14 @@ from .pointwise_convolution import PointwiseConvLayer
 
 
 def _add(a, b):
+    if act_dtype(a) != act_dtype(b):
+        raise ValueError("residual backward of mixed storage types: {} vs {}".format(act_dtype(a), act_dtype(b)))
     a, b = to_nhwc(a), to_nhwc(b)
     if a.shape != b.shape:
         raise ValueError("residual backward shape mismatch: {} vs {}".format(tuple(a.shape), tuple(b.shape)))
-    out = empty_nhwc(*a.shape)
-    lib.dk_add_f32(a.data_ptr(), b.data_ptr(), a.numel(), 0, out.data_ptr(), 0, stream_handle())
+    add = lib.dk_add_bf16 if a.dtype == BF16 else lib.dk_add_f32
+    out = empty_nhwc(*a.shape, dtype=a.dtype)
+    add(a.data_ptr(), b.data_ptr(), a.numel(), 0, out.data_ptr(), 0, stream_handle())
     return out
 
 

@@ -291,6 +291,13 @@ for _n in ("dk_pwconv_fwd_ex", "dk_pwconv_dgrad_ex", "dk_pwconv_wgrad_bnx", "dk_
     if _n + "_f32" in MODEL:
         MODEL[_n + "_bf16"] = _half(MODEL[_n + "_f32"])
 
-# host-side queries of the bf16 dense convolution: no device work
-for _n in ("dk_conv2d_fwd_bf16_stats_rows", "dk_conv2d_wgrad_bf16_workspace_bytes"):
+# the residual join with bf16 storage: the fp32 entries' flops, three 2-byte activation streams, and the
+# mask bytes as they are (1 per element) -- with a mask 7 bytes per element against fp32's 13
+MODEL["dk_add_bf16"] = lambda a, b, n, relu, y, mask, st: (n, 2 * 3 * n + (n if mask else 0))
+MODEL["dk_bn_add_bf16"] = lambda a, am, ai, ag, ab, ar, b, bm, bi, bg, bb, br, n, C, relu, y, mask, st: (
+    n * (1 + 4 * (bool(am) + bool(bm))), 2 * 3 * n + (n if mask else 0))
+MODEL["dk_relu_bwd_bn_partial_bf16"] = lambda dy, mask, x, P, C, *rest: (4 * P * C, 2 * 3 * P * C + P * C)
+
+# host-side queries of the bf16 entries: no device work
+for _n in ("dk_conv2d_fwd_bf16_stats_rows", "dk_conv2d_wgrad_bf16_workspace_bytes", "dk_pwconv_dgrad_bf16_stats_rows"):
     MODEL[_n] = lambda *a: (0, 0)

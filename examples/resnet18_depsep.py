@@ -5,6 +5,7 @@ biases, regularisers and initialisation order as the reference class, so a fixed
 ``np.random.seed`` gives the reference's initial weights.
 
     python examples/resnet18_depsep.py --steps 5        # synthetic-data training loop
+    python examples/resnet18_depsep.py --steps 5 --bf16 # the same with bf16 activation storage
 """
 from __future__ import annotations
 
@@ -128,6 +129,9 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--batch", type=int, default=60)
     ap.add_argument("--steps", type=int, default=5)
+    ap.add_argument("--bf16", action="store_true",
+                    help="feed the batch as bf16: every activation and activation gradient is stored in bf16 "
+                         "(parameters, statistics and weight gradients stay fp32)")
     args = ap.parse_args()
     np.random.seed(0)
     net = ResNet18("DogsImageNet225ResNet18DepSep")
@@ -135,6 +139,8 @@ def main():
     sgd = SGDMomentum(net, 0.05 * (args.batch / 200.0), 0.9)
     X, y, onehot = synthetic_batch(args.batch)
     X, onehot = as_device(X), as_device(onehot)
+    if args.bf16:
+        X = X.to(torch.bfloat16)
     for i in range(args.steps):
         t0 = time.time()
         loss, scores = net.forward(X, onehot)

@@ -259,12 +259,27 @@ int dk_bn_bwd_apply_bf16(const uint16_t* x, const uint16_t* dy, long long numel,
 int dk_bn_bwd_bf16(const uint16_t* x, const uint16_t* dy, int P, int C, const float* mean, const float* invstd, const float* gamma, const float* beta, int relu, float* dgamma, float* dbeta, uint16_t* dx, void* ws, size_t ws_bytes, void* stream);
 int dk_relu_fwd_bf16(const uint16_t* x, long long n, uint16_t* y, uint8_t* mask, void* stream);
 int dk_relu_bwd_bf16(const uint16_t* dy, const uint8_t* mask, long long n, uint16_t* dx, void* stream);
+/* The residual join with bf16 storage (twins of dk_add_f32 / dk_bn_add_f32, residual_block.py:65-75; and of
+ * dk_relu_bwd_bn_partial_f64, residual_block.py:85-86).  a, b, y (dy, x, dx) bf16, 8-byte aligned; the
+ * fp32 operations of the fp32 entries in their order on the widened operands, the mask (nullable)
+ * v > 0 taken in fp32 before the one rounding of y.  dk_bn_add_bf16: C % 4 == 0, n % C == 0; 16-byte
+ * accesses when C % 8 == 0.  dk_relu_bwd_bn_partial_bf16: dx = mask ? dy : 0 (exact), part has
+ * dk_bn_partial_blocks(P, C) rows and takes an in-launch fold arming (dk_bn_fold_arm_bwd). */
+int dk_add_bf16(const uint16_t* a, const uint16_t* b, long long n, int relu, uint16_t* y, uint8_t* mask, void* stream);
+int dk_bn_add_bf16(const uint16_t* a, const float* a_mean, const float* a_invstd, const float* a_gamma, const float* a_beta, int a_relu, const uint16_t* b, const float* b_mean, const float* b_invstd, const float* b_gamma, const float* b_beta, int b_relu, long long n, int C, int relu, uint16_t* y, uint8_t* mask, void* stream);
+int dk_relu_bwd_bn_partial_bf16(const uint16_t* dy, const uint8_t* mask, const uint16_t* x, int P, int C, const float* mean, const float* invstd, const float* gamma, const float* beta, int relu, uint16_t* dx, void* part, size_t part_bytes, void* stream);
 int dk_pwconv_fwd_bf16_stats_rows(int N, int OH, int OW, int K, int C);
 /* dk_pwconv_fwd_ex_bf16 at stride > 1 never takes the streaming kernels (their rows are what the query
  * above returns for K, C in {64, 128} and the deep shapes): its rows at any stride. */
 int dk_pwconv_fwd_bf16_strided_stats_rows(int N, int OH, int OW, int K, int C, int stride);
 int dk_pwconv_fwd_ex_bf16(const uint16_t* x, int N, int H, int W, int C, const float* w_kc, int K, int stride, const float* bias, uint16_t* y, int OH, int OW, const float* bn_mean, const float* bn_invstd, const float* bn_gamma, const float* bn_beta, int bn_relu, double* stats, void* stream);
 int dk_pwconv_dgrad_ex_bf16(const uint16_t* dy, int N, int OH, int OW, int K, const float* w_kc, int C, int stride, uint16_t* dx, const uint16_t* residual, const uint16_t* bn_x, const float* bn_mean, const float* bn_invstd, const float* bn_gamma, const float* bn_beta, int bn_relu, double* part, void* stream);
+/* dk_pwconv_dgrad_ex_bf16 takes stride 1..8 (dk_pwconv_dgrad_ex_f32's rules: for stride > 1 dx and bn_x are
+ * the widened N x (OH*stride) x (OW*stride) x C grid, dx exactly 0 off the sampling lattice -- or, without
+ * part, equal to the residual there; part together with residual at stride > 1 returns 10001).  The
+ * partials are taken over the rounded stored lattice values.  part has
+ * dk_pwconv_dgrad_bf16_stats_rows(N, OH, OW, K, C, stride) rows: the tile the launch itself picks. */
+int dk_pwconv_dgrad_bf16_stats_rows(int N, int OH, int OW, int K, int C, int stride);
 int dk_pwconv_wgrad_bnx_bf16(const uint16_t* dy, const uint16_t* x, int N, int H, int W, int C, int K, int stride, int OH, int OW, const float* w_kc, float l2, float* dw_kc, void* ws, size_t ws_bytes, const float* bn_mean, const float* bn_invstd, const float* bn_gamma, const float* bn_beta, int bn_relu, void* stream);
 int dk_dwconv_fwd_ex_bf16(const uint16_t* x, int N, int H, int W, int C, const float* w_crs, int R, int S, int stride, int pad, const float* bias, uint16_t* y, int OH, int OW, const float* bn_mean, const float* bn_invstd, const float* bn_gamma, const float* bn_beta, int bn_relu, double* stats, void* stream);
 int dk_dwconv_dgrad_ex_bf16(const uint16_t* dy, int N, int OH, int OW, int C, const float* w_crs, int R, int S, int stride, int pad, uint16_t* dx, int H, int W, void* ws, size_t ws_bytes, const uint16_t* residual, const uint16_t* bn_x, const float* bn_mean, const float* bn_invstd, const float* bn_gamma, const float* bn_beta, int bn_relu, double* part, void* stream);

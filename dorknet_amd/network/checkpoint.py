@@ -3,7 +3,8 @@
 Reference: each layer's ``save_to_h5`` / ``load_from_h5`` (layers/convolution.py:226-281,
 layers/depthwise_convolution.py:300-353, layers/pointwise_convolution.py:77-130,
 layers/dense_layer.py:69-117, layers/batch_norm.py:176-232, layers/activations.py:49-55,
-layers/pooling.py:38-44, layers/losses.py:36-42, layers/residual_block.py:99-151) and
+layers/pooling.py:38-44 (MaxPoolLayer, :45-77, has none there: its ``stride`` entry is an
+extension), layers/losses.py:36-42, layers/residual_block.py:99-151) and
 ``FeedForwardNetwork.save_weights_to_h5`` / ``load_network_from_json_and_h5``
 (network/feed_forward_network.py:90-139).
 
@@ -277,6 +278,20 @@ def _load_plain(layer, open_f, load_grads):
     pass
 
 
+def _save_maxpool(layer, open_f, save_grads):
+    """An extension: the reference's MaxPoolLayer (layers/pooling.py:45-77) has no checkpoint methods."""
+    d = _info(open_f, layer)
+    d.attrs["stride"] = int(layer.stride)
+
+
+def _load_maxpool(layer, open_f, load_grads):
+    stride = int(_attrs(open_f, layer)["stride"])
+    if not 1 <= stride <= layer.MAX_STRIDE:
+        raise ValueError("MaxPoolLayer {}: stored stride {} is outside 1..{}".format(layer.layer_name, stride,
+                                                                                      layer.MAX_STRIDE))
+    layer.stride = stride
+
+
 def _new_layer(l_type, name):
     from ..layers.activations import ReLu
     from ..layers.batch_norm import BatchNormLayer
@@ -285,10 +300,10 @@ def _new_layer(l_type, name):
     from ..layers.depthwise_convolution import DepthwiseConvLayer
     from ..layers.losses import SoftmaxWithCrossEntropy
     from ..layers.pointwise_convolution import PointwiseConvLayer
-    from ..layers.pooling import GlobalAveragePoolingLayer
+    from ..layers.pooling import GlobalAveragePoolingLayer, MaxPoolLayer
     from ..layers.residual_block import ResidualBlock
     classes = {c.__name__: c for c in (ConvLayer, BatchNormLayer, ReLu, DepthwiseConvLayer, PointwiseConvLayer,
-                                       GlobalAveragePoolingLayer, DenseLayer, ResidualBlock,
+                                       GlobalAveragePoolingLayer, MaxPoolLayer, DenseLayer, ResidualBlock,
                                        SoftmaxWithCrossEntropy)}
     if l_type not in classes:
         raise ValueError("unknown layer type {!r} for layer {!r}".format(l_type, name))
@@ -351,6 +366,7 @@ _HANDLERS = {
     "BatchNormLayer": (_save_bn, _load_bn),
     "ReLu": (_save_plain, _load_plain),
     "GlobalAveragePoolingLayer": (_save_plain, _load_plain),
+    "MaxPoolLayer": (_save_maxpool, _load_maxpool),
     "SoftmaxWithCrossEntropy": (_save_plain, _load_plain),
     "ResidualBlock": (_save_residual, _load_residual),
 }

@@ -508,6 +508,24 @@ int dk_gap_fwd_f32(const float* x, int N, int HW, int C, float* out, void* strea
  * dk_bn_add_f32 followed by dk_gap_fwd_f32, y's ReLU mask (N*HW*C bytes, NHWC) written when non-NULL. */
 int dk_gap_join_fwd_f32(const float* a, const float* a_mean, const float* a_invstd, const float* a_gamma, const float* a_beta, int a_relu, const float* b, const float* b_mean, const float* b_invstd, const float* b_gamma, const float* b_beta, int b_relu, int N, int HW, int C, uint8_t* mask, float* out, void* stream);
 int dk_gap_bwd_f32(const float* dy, int N, int HW, int C, float* dx, void* stream);
+/* Max pooling (layers/pooling.py:45-77, layers/pooling_cy.pyx:8-88; dorknet_amd/csrc/maxpool.hip), NHWC.
+ * Window stride x stride, non-overlapping; OH = H / stride, OW = W / stride: the trailing H % stride rows
+ * and W % stride columns are not pooled (the reference reads out of bounds there) and get a zero gradient.
+ * The window is scanned row-major from (0, 0) with a strict >: the first maximum wins (pool_train).
+ *   dk_maxpool_fwd_*: y[N][OH][OW][C] and, when idx != NULL (training), idx[N][OH][OW][C]: one uint8 per
+ *     output element holding m * stride + n (the reference keeps an int32 map the size of the input);
+ *     idx == NULL is the test-mode forward.  bf16 in, bf16 out: max and copy are exact.
+ *   dk_maxpool_fwd_bnx_*: the same over BN(x) [+ ReLU] formed on load (see *_bnx_*; dk_bn_apply_*'s
+ *     arithmetic, for bf16 rounded to bf16 before the comparison): bit-identical to apply-then-pool.
+ *   dk_maxpool_bwd_*: dx[N][H][W][C] = dy at the recorded location, 0 everywhere else, the trailing rows
+ *     and columns included; every element is written exactly once (no memset, no atomics).
+ * DK_ERR_ARGS: stride outside 1..16, any of N, H, W, C below 1, OH or OW equal to 0, a NULL tensor. */
+int dk_maxpool_fwd_f32(const float* x, int N, int H, int W, int C, int stride, float* y, uint8_t* idx, void* stream);
+int dk_maxpool_fwd_bf16(const uint16_t* x, int N, int H, int W, int C, int stride, uint16_t* y, uint8_t* idx, void* stream);
+int dk_maxpool_fwd_bnx_f32(const float* x, int N, int H, int W, int C, int stride, const float* bn_mean, const float* bn_invstd, const float* bn_gamma, const float* bn_beta, int bn_relu, float* y, uint8_t* idx, void* stream);
+int dk_maxpool_fwd_bnx_bf16(const uint16_t* x, int N, int H, int W, int C, int stride, const float* bn_mean, const float* bn_invstd, const float* bn_gamma, const float* bn_beta, int bn_relu, uint16_t* y, uint8_t* idx, void* stream);
+int dk_maxpool_bwd_f32(const float* dy, const uint8_t* idx, int N, int H, int W, int C, int stride, float* dx, void* stream);
+int dk_maxpool_bwd_bf16(const uint16_t* dy, const uint8_t* idx, int N, int H, int W, int C, int stride, uint16_t* dx, void* stream);
 int dk_softmax_xent_fwd_f32(const float* x, const float* y_onehot, int B, int K, float* p, float* loss, void* stream);
 int dk_softmax_xent_bwd_f32(const float* p, const float* y_onehot, int B, int K, float* dx, void* stream);
 

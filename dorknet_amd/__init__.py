@@ -19,7 +19,7 @@ _ALIASES = [
     "layers.pointwise_convolution", "layers.dense_layer", "layers.batch_norm", "layers.activations",
     "layers.residual_block", "layers.pooling", "layers.losses",
     "network", "network.feed_forward_network",
-    "optimisers", "optimisers.SGDMomentum",
+    "optimisers", "optimisers.SGDMomentum", "optimisers.SGD", "optimisers.RMSProp",
     "regularisers", "regularisers.l2",
 ]
 

@@ -382,8 +382,9 @@ __global__ void softmax_xent_bwd_kernel(const float* __restrict__ p, const float
   dx[i] = (1.0f / (float)B) * (p[i] - y[i]);
 }
 
-// Multi-tensor SGD momentum: for every listed tensor t and element i
-//   d = (-lr) * g + mom * v;  w += d;  v = d      (SGDMomentum.py:33-39, same op order)
+// Multi-tensor optimiser updates: one launch over a table of tensors, one block per 256 elements.
+// The state pointer v is SGD momentum's velocity, RMSProp's squared-gradient cache, and unused
+// (null) for plain SGD.
 struct SgdEntry {
   float* w;
   const float* g;
@@ -393,8 +394,9 @@ struct SgdEntry {
 };
 
 constexpr int kSgdLdsTable = 1024;
-__global__ __launch_bounds__(256) void sgd_momentum_multi_kernel(const SgdEntry* __restrict__ tab, int ntens,
-                                                                 float lr, float mom, float gscale) {
+// The table entry owning this block and this thread's element index in it (>= e.n past the
+// tensor's end).  Called by all 256 threads of the block (it holds barriers).
+__device__ __forceinline__ long long multi_tensor_owner(const SgdEntry* __restrict__ tab, int ntens, SgdEntry& e) {
   // find the tensor owning this block: the block0 column is loaded into LDS in parallel (one
   // load latency) and searched there; the old linear scan of the global table was ~100
   // dependent loads for the last blocks.
@@ -418,13 +420,58 @@ __global__ __launch_bounds__(256) void sgd_momentum_multi_kernel(const SgdEntry*
   } else {
     while (t + 1 < ntens && tab[t + 1].block0 <= b) ++t;
   }
-  const SgdEntry e = tab[t];
-  const long long i = (b - e.block0) * 256 + threadIdx.x;
+  e = tab[t];
+  return (b - e.block0) * 256 + threadIdx.x;
+}
+
+// SGD momentum: for every listed tensor t and element i
+//   d = (-lr) * g + mom * v;  w += d;  v = d      (SGDMomentum.py:33-39, same op order)
+__global__ __launch_bounds__(256) void sgd_momentum_multi_kernel(const SgdEntry* __restrict__ tab, int ntens,
+                                                                 float lr, float mom, float gscale) {
+  SgdEntry e;
+  const long long i = multi_tensor_owner(tab, ntens, e);
   if (i >= e.n) return;
   const float g = gscale == 1.0f ? e.g[i] : __fmul_rn(gscale, e.g[i]);
   const float d = __fadd_rn(__fmul_rn(-lr, g), __fmul_rn(mom, e.v[i]));
   e.w[i] = __fadd_rn(e.w[i], d);
   e.v[i] = d;
+}
+
+// One fp32 operation, one rounding.  __fmul_rn / __fadd_rn are plain * and + compiled under the
+// default contraction mode, and once inlined a product and the sum it feeds may still fuse: plain
+// SGD's w + (-lr) * g came out as one v_fma_f32.  An operation compiled with contraction off
+// carries no contract flag and is never fused.
+__device__ __forceinline__ float mul_1r(float a, float b) {
+#pragma clang fp contract(off)
+  return a * b;
+}
+__device__ __forceinline__ float add_1r(float a, float b) {
+#pragma clang fp contract(off)
+  return a + b;
+}
+
+// Plain SGD:  d = (-lr) * g;  w += d      (SGD.py:20-24)
+__global__ __launch_bounds__(256) void sgd_multi_kernel(const SgdEntry* __restrict__ tab, int ntens, float lr) {
+  SgdEntry e;
+  const long long i = multi_tensor_owner(tab, ntens, e);
+  if (i >= e.n) return;
+  e.w[i] = add_1r(e.w[i], mul_1r(-lr, e.g[i]));
+}
+
+// RMSProp:  c = decay * c + (1 - decay) * (g * g);  d = ((-lr) * g) / sqrt(c + eps);  w += d
+// (RMSProp.py:28-36, same op order).  Every operation is one correctly rounded fp32 operation: no
+// contraction (above), sqrtf (v_sqrt_f32 plus its residual correction; __fsqrt_rn is the bare
+// 1-ulp instruction) and the full division sequence.
+__global__ __launch_bounds__(256) void rmsprop_multi_kernel(const SgdEntry* __restrict__ tab, int ntens, float lr,
+                                                            float decay, float one_minus_decay, float eps) {
+  SgdEntry e;
+  const long long i = multi_tensor_owner(tab, ntens, e);
+  if (i >= e.n) return;
+  const float g = e.g[i];
+  const float c = add_1r(mul_1r(decay, e.v[i]), mul_1r(one_minus_decay, mul_1r(g, g)));
+  const float d = __fdiv_rn(mul_1r(-lr, g), sqrtf(add_1r(c, eps)));
+  e.w[i] = add_1r(e.w[i], d);
+  e.v[i] = c;
 }
 
 // out[0] = 0.5 * strength * sum w^2 (one block, fp64 accumulate).  With accumulate != 0,
@@ -763,6 +810,28 @@ DK_API int dk_sgd_momentum_multi_f32(const void* table, int ntens, long long tot
   if (ntens <= 0) return 0;
   hipLaunchKernelGGL(sgd_momentum_multi_kernel, dim3((unsigned)total_blocks), dim3(256), 0, as_stream(stream),
                      static_cast<const SgdEntry*>(table), ntens, lr, momentum, grad_scale);
+  return launch_status();
+}
+
+// The same table for plain SGD (state pointer unused, 0) and RMSProp (state = the cache).
+static bool multi_args_ok(const void* table, int ntens, long long total_blocks) {
+  return ntens >= 0 && total_blocks >= 0 && total_blocks <= 0x7fffffffll && (table || ntens == 0);
+}
+
+DK_API int dk_sgd_multi_f32(const void* table, int ntens, long long total_blocks, float lr, void* stream) {
+  if (!multi_args_ok(table, ntens, total_blocks)) return DK_ERR_ARGS;
+  if (ntens == 0 || total_blocks == 0) return 0;
+  hipLaunchKernelGGL(sgd_multi_kernel, dim3((unsigned)total_blocks), dim3(256), 0, as_stream(stream),
+                     static_cast<const SgdEntry*>(table), ntens, lr);
+  return launch_status();
+}
+
+DK_API int dk_rmsprop_multi_f32(const void* table, int ntens, long long total_blocks, float lr, float decay,
+                                float one_minus_decay, float eps, void* stream) {
+  if (!multi_args_ok(table, ntens, total_blocks)) return DK_ERR_ARGS;
+  if (ntens == 0 || total_blocks == 0) return 0;
+  hipLaunchKernelGGL(rmsprop_multi_kernel, dim3((unsigned)total_blocks), dim3(256), 0, as_stream(stream),
+                     static_cast<const SgdEntry*>(table), ntens, lr, decay, one_minus_decay, eps);
   return launch_status();
 }
 

@@ -1,0 +1,200 @@
+"""What the optimisers share: parameter discovery, the DataParallel flag handshake, the device
+table of the multi-tensor kernels (dorknet_amd/csrc/elementwise.hip) and the state file.
+
+Parameter discovery is the reference's SGDMomentum.py:7-14: every top-level layer with
+``learned_params`` plus one level of ``layer_list``, skip projections only with
+``update_skip_projections=True`` (an extension).  The reference's SGD.py:8-11 and
+RMSProp.py:12-15 loop over ``layer_list`` too but test and append ``layer`` (the block, whose own
+``learned_params`` is None) where SGDMomentum.py uses ``l``: a typo under which nothing inside a
+ResidualBlock is ever updated.  All three optimisers here use SGDMomentum's discovery.
+
+The table has one 40-byte row ``{w, g, state, n, first_block}`` per parameter tensor (``state``:
+the velocity or the squared-gradient cache, 0 for plain SGD), 256 elements per block.  It is
+built at the first ``update_weights`` and again only when a pointer or a size changes; the
+scalars travel as kernel arguments.  After that an update is one launch: no allocation, no host
+synchronisation.
+
+State file (``save_state_to_h5`` / ``load_state_from_h5``; its own file, not the weights file):
+a group ``optimiser`` with the attributes ``type`` (the class name), ``learning_rate``,
+``momentum`` or ``decay_rate`` where the class has one, ``update_skip_projections``, and one fp32
+dataset ``optimiser/<layer_name>/<param>`` per state tensor, in the parameter's shape.
+"""
+from __future__ import annotations
+
+import numpy as np
+import torch
+
+from .._hip import stream_handle
+
+
+def discover_learnable_layers(network, update_skip_projections=False):
+    out = []
+    for layer in network.layers:
+        if layer.learned_params is not None:
+            out.append(layer)
+        if hasattr(layer, "layer_list"):  # For composite layers like ResidualBlock
+            for l in layer.layer_list:
+                if l.learned_params is not None:
+                    out.append(l)
+            skip = getattr(layer, "skip_projection", None)
+            if update_skip_projections and skip is not None and skip.learned_params:
+                out.append(skip)
+    return out
+
+
+class MultiTensorOptimiser:
+    """Base of SGD, SGDMomentum and RMSProp.  A subclass names its extra hyper-parameter in
+    ``_HYPER`` (also the state file's attribute), says in ``_HAS_STATE`` whether it keeps a state
+    tensor per parameter (``grad_cache``), and launches its kernel in ``_launch``."""
+
+    _HYPER = ()
+    _HAS_STATE = True
+    _STATE_WORDS = ("parameters, grads and state", "grad / state")
+
+    def __init__(self, network, learning_rate, update_skip_projections=False):
+        name = type(self).__name__
+        self.network = network
+        self.update_skip_projections = update_skip_projections
+        # a data-parallel wrapper must all-reduce exactly the gradients this optimiser applies
+        # (parallel.DataParallel checks the same pair from its side)
+        dp_flag = getattr(network, "_dp_update_skip_projections", None)
+        if dp_flag is not None and dp_flag != update_skip_projections:
+            raise ValueError("{}(update_skip_projections={}) disagrees with DataParallel's "
+                             "update_skip_projections={}: skip-projection gradients would be applied "
+                             "un-averaged".format(name, update_skip_projections, dp_flag))
+        try:
+            network._opt_update_skip_projections = update_skip_projections
+        except AttributeError:
+            pass
+        self.learnable_layers = discover_learnable_layers(network, update_skip_projections)
+        self.learning_rate = learning_rate
+        if self._HAS_STATE:
+            self.grad_cache = {}
+            for layer in self.learnable_layers:
+                layer_d = {}
+                for k, v in layer.grads.items():
+                    layer_d[k] = torch.zeros_like(v) if isinstance(v, torch.Tensor) else np.zeros_like(v)
+                self.grad_cache[layer] = layer_d
+        self._table = None
+        self._table_sig = None
+        self._total_blocks = 0
+
+    def set_learning_rate(self, new_lr):
+        self.learning_rate = new_lr
+
+    def multiply_learning_rate(self, multiplier):
+        self.learning_rate *= multiplier
+
+    # -- the device table ---------------------------------------------------------------------
+
+    def _entries(self):
+        out = []
+        for layer in self.learnable_layers:
+            for param in layer.learned_params.keys():
+                w = layer.learned_params[param]
+                g = layer.grads[param]
+                v = self.grad_cache[layer][param] if self._HAS_STATE else None
+                out.append((w, g, v))
+        return out
+
+    def _build_table(self, entries):
+        name = type(self).__name__
+        rows = []
+        block0 = 0
+        for w, g, v in entries:
+            for t in (w, g, v) if self._HAS_STATE else (w, g):
+                if not (isinstance(t, torch.Tensor) and t.is_cuda and t.dtype == torch.float32
+                        and t.is_contiguous()):
+                    raise RuntimeError("{}: {} must be contiguous fp32 device tensors (build the optimiser "
+                                       "after network.to_gpu())".format(name, self._STATE_WORDS[0]))
+            n = w.numel()
+            if g.numel() != n or (v is not None and v.numel() != n):
+                raise ValueError("{}: {} size mismatch".format(name, self._STATE_WORDS[1]))
+            rows.append((w.data_ptr(), g.data_ptr(), 0 if v is None else v.data_ptr(), n, block0))
+            block0 += -(-n // 256)
+        table = np.array(rows, dtype=np.int64).reshape(-1, 5)
+        self._table = torch.as_tensor(table, device="cuda")
+        self._total_blocks = block0
+
+    def _launch(self, table, ntens, total_blocks, stream):
+        raise NotImplementedError
+
+    def update_weights(self):
+        entries = self._entries()
+        try:
+            if self._HAS_STATE:
+                sig = tuple((w.data_ptr(), g.data_ptr(), v.data_ptr(), w.numel()) for w, g, v in entries)
+            else:
+                sig = tuple((w.data_ptr(), g.data_ptr(), 0, w.numel()) for w, g, _ in entries)
+        except AttributeError:  # host arrays: _build_table says what is wrong
+            sig = None
+        if sig is None or sig != self._table_sig:
+            self._build_table(entries)
+            self._table_sig = sig
+        self._launch(self._table.data_ptr(), len(entries), self._total_blocks, stream_handle())
+
+    # -- the state file -----------------------------------------------------------------------
+
+    def _state_items(self):
+        """[(dataset path, state tensor or array)], refusing layer names that would collide."""
+        seen = set()
+        for layer in self.learnable_layers:
+            if layer.layer_name in seen:
+                raise ValueError("{}: two learnable layers are named {!r}; the state file keys its "
+                                 "datasets by layer name".format(type(self).__name__, layer.layer_name))
+            seen.add(layer.layer_name)
+        if not self._HAS_STATE:
+            return []
+        return [("optimiser/{}/{}".format(layer.layer_name, k), v)
+                for layer in self.learnable_layers for k, v in self.grad_cache[layer].items()]
+
+    def save_state_to_h5(self, fname):
+        from ..network.checkpoint import _write, open_h5
+        items = self._state_items()
+        with open_h5(fname, "w") as f:
+            g = f.create_group("optimiser")
+            g.attrs["type"] = type(self).__name__
+            g.attrs["learning_rate"] = np.float64(self.learning_rate)
+            for h in self._HYPER:
+                g.attrs[h] = np.float64(getattr(self, h))
+            g.attrs["update_skip_projections"] = bool(self.update_skip_projections)
+            for path, v in items:
+                _write(f, path, v)
+
+    def load_state_from_h5(self, fname):
+        """Restore the hyper-parameters and copy the stored state into the existing state tensors
+        in place (the device table stays valid).  Everything is read and checked first: a
+        ValueError leaves the optimiser as it was."""
+        from ..network.checkpoint import _as_str, open_h5
+        name = type(self).__name__
+        items = self._state_items()
+        with open_h5(fname, "r") as f:
+            if "optimiser" not in f:
+                raise ValueError("{}: {} holds no optimiser state".format(name, fname))
+            attrs = f["optimiser"].attrs
+            stored = _as_str(attrs["type"]) if "type" in attrs else None
+            if stored != name:
+                raise ValueError("{}: {} holds the state of a {}".format(name, fname, stored))
+            for h in ("learning_rate", *self._HYPER, "update_skip_projections"):
+                if h not in attrs:
+                    raise ValueError("{}: {} has no attribute {!r}".format(name, fname, h))
+            if bool(attrs["update_skip_projections"]) != bool(self.update_skip_projections):
+                raise ValueError("{}: {} was saved with update_skip_projections={}".format(
+                    name, fname, bool(attrs["update_skip_projections"])))
+            scalars = {h: float(attrs[h]) for h in ("learning_rate", *self._HYPER)}
+            values = []
+            for path, v in items:
+                if path not in f:
+                    raise ValueError("{}: {} has no dataset {}".format(name, fname, path))
+                d = f[path]
+                if d.shape is None or tuple(d.shape) != tuple(v.shape):
+                    raise ValueError("{}: dataset {} has shape {}, the state tensor {}".format(
+                        name, path, d.shape, tuple(v.shape)))
+                values.append(np.ascontiguousarray(d[:], dtype=np.float32))
+        for (_, v), a in zip(items, values):
+            if isinstance(v, torch.Tensor):
+                v.copy_(torch.from_numpy(a))
+            else:
+                v[...] = a
+        for h, x in scalars.items():
+            setattr(self, h, x)

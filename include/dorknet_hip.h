@@ -535,10 +535,20 @@ int dk_softmax_xent_bwd_f32(const float* p, const float* y_onehot, int B, int K,
  *   the reference issues ~4 CuPy kernels per tensor).  Table entry (40 bytes):
  *   { float* w; const float* g; float* v; int64 n; int64 first_block }, first_block =
  *   sum of ceil(n/256) over the preceding entries; total_blocks = that sum over all.
+ *   Plain SGD (optimisers/SGD.py:20-24) and RMSProp (optimisers/RMSProp.py:28-36; NumPy only in
+ *   the reference) take the same table: the third pointer is RMSProp's squared-gradient cache
+ *   and is unused (0) for SGD.  Per element, each operation rounded once to fp32, in this order:
+ *     dk_sgd_multi_f32:      d = (-lr) * g;  w = w + d
+ *     dk_rmsprop_multi_f32:  c = decay * c + one_minus_decay * (g * g);
+ *                            d = ((-lr) * g) / sqrt(c + eps);  w = w + d;  c stored back
+ *   (the reference's eps is 1e-5; one_minus_decay is 1 - decay formed in double by the caller).
+ *   Both return DK_ERR_ARGS for a NULL table with ntens > 0 or a negative count.
  *   l2 loss term: regularisers/l2.py:12-14; scale: l2.py:16-17 and DP averaging.
  *   colsum: bias gradients, np.sum(upstream_dx, axis=(0,2,3)) (convolution.py:91-92 etc.).
  * ------------------------------------------------------------------------------------- */
 int dk_sgd_momentum_multi_f32(const void* table, int ntens, long long total_blocks, float lr, float momentum, float grad_scale, void* stream);
+int dk_sgd_multi_f32(const void* table, int ntens, long long total_blocks, float lr, void* stream);
+int dk_rmsprop_multi_f32(const void* table, int ntens, long long total_blocks, float lr, float decay, float one_minus_decay, float eps, void* stream);
 int dk_l2_loss_f32(const float* w, long long n, float strength, int accumulate, float* out, void* stream);
 size_t dk_l2_multi_workspace_bytes(long long total_blocks);
 int dk_l2_loss_multi_f32(const void* table, int ntens, long long total_blocks, const float* add_to, float* out, void* ws, size_t ws_bytes, void* stream);

@@ -1,0 +1,70 @@
+"""update_weights of the three optimisers over ResNet-18-depsep's parameter set (104 tensors,
+1,336,312 parameters; examples/resnet18_depsep.py): SGDMomentum (dk_sgd_momentum_multi_f32), SGD
+(dk_sgd_multi_f32) and RMSProp (dk_rmsprop_multi_f32), one multi-tensor launch each.  HIP events
+around --calls back-to-back update_weights() after a warm-up, --repeats times, the optimisers
+taking turns within a repeat; per call: the median over the repeats and their min-max.  Then the
+same for the C entry alone on the table update_weights() built (no Python walk over the tensors):
+back-to-back update_weights() calls are paced by the host, the entry alone by the launches.  All
+three share the network's parameters and gradients; the gradients are small, so the weights stay
+finite.
+    python scripts/optimiser_bench.py [--calls 100] [--repeats 5]
+"""
+import argparse
+import os
+import sys
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+
+import numpy as np  # noqa: E402
+import torch  # noqa: E402
+
+from dorknet_amd._hip import stream_handle  # noqa: E402
+from dorknet_amd.optimisers.RMSProp import RMSProp  # noqa: E402
+from dorknet_amd.optimisers.SGD import SGD  # noqa: E402
+from dorknet_amd.optimisers.SGDMomentum import SGDMomentum  # noqa: E402
+from examples.resnet18_depsep import ResNet18  # noqa: E402
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--calls", type=int, default=100)
+    ap.add_argument("--repeats", type=int, default=5)
+    a = ap.parse_args()
+    np.random.seed(0)
+    net = ResNet18("bench")
+    net.to_gpu()
+    opts = [("SGDMomentum", SGDMomentum(net, 1e-4, 0.9)), ("SGD", SGD(net, 1e-4)),
+            ("RMSProp", RMSProp(net, 1e-6, 0.9))]
+    layers = opts[0][1].learnable_layers
+    torch.manual_seed(0)
+    for l in layers:
+        for k, g in l.grads.items():
+            g.copy_(1e-3 * torch.randn_like(g))
+    ntens = sum(len(l.learned_params) for l in layers)
+    nparam = sum(v.numel() for l in layers for v in l.learned_params.values())
+    st = stream_handle()
+
+    def entry_only(opt):  # the C entry on the table update_weights built: the launch without the Python walk
+        opt._launch(opt._table.data_ptr(), ntens, opt._total_blocks, st)
+
+    for what, call in (("update_weights()", lambda opt: opt.update_weights()), ("the C entry alone", entry_only)):
+        times = {name: [] for name, _ in opts}
+        for r in range(a.repeats + 1):  # repeat 0 is the warm-up (and builds the tables)
+            for name, opt in opts:
+                e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                e0.record()
+                for _ in range(a.calls):
+                    call(opt)
+                e1.record()
+                e1.synchronize()
+                if r:
+                    times[name].append(1e3 * e0.elapsed_time(e1) / a.calls)
+        print("{} tensors, {} parameters; us per call of {} over {} back-to-back calls, {} repeats".format(
+            ntens, nparam, what, a.calls, a.repeats))
+        for name, _ in opts:
+            t = sorted(times[name])
+            print("  {:12s} median {:7.2f}  min {:7.2f}  max {:7.2f}".format(name, t[len(t) // 2], t[0], t[-1]))
+
+
+if __name__ == "__main__":
+    main()

@@ -108,3 +108,12 @@ def log_slack(name, err, want64, want32):
         f.write("{}\t{:.3e}\t{:.3e}\t{}\n".format(name, err / max(rel, 1e-300), ref / max(rel, 1e-300),
                                                   "inf" if ref == 0 else "{:.3f}".format(err / ref)))
 
+
+def log_ratio(name, ratio):
+    """With DORKNET_SLACK_LOG=<file>: append "dw<TAB>name<TAB>worst err / bound" for a per-element check
+    (tests/_dw_ref.py:check) -- a recorded result, not a tolerance; log_slack's lines are the normwise tests'."""
+    import os
+    path = os.environ.get("DORKNET_SLACK_LOG")
+    if path:
+        with open(path, "a") as f:
+            f.write("dw\t{}\t{:.4f}\n".format(name, ratio))

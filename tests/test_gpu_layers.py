@@ -115,6 +115,11 @@ DW_CASES = [
     (8, 5, 5, 2, 2, 2, 13, 12, False),    # 5x5 stride-2 sub-pixel dgrad
     (4, 1, 1, 2, 0, 2, 9, 8, True),       # 1x1 stride-2
     (24, 3, 3, 2, 0, 1, 10, 11, False),   # stride 2 without a sub-pixel kernel (gather path)
+    (8, 3, 3, 1, 0, 2, 13, 11, False),    # stride 1 without padding: the dgrad is the forward kernel at padding 2
+    (8, 5, 5, 1, 0, 2, 9, 10, True),      # 5x5 without padding: dgrad padding 4
+    (8, 3, 3, 1, 2, 1, 5, 6, False),      # padding R - 1: output larger than input, dgrad padding 0
+    (8, 1, 1, 1, 0, 2, 6, 5, True),       # 1x1 stride 1
+    (1028, 3, 3, 1, 1, 1, 3, 3, False),   # C / 4 = 257: the weight gradient's second channel block
 ]
 
 

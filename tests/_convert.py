@@ -109,11 +109,12 @@ def log_slack(name, err, want64, want32):
                                                   "inf" if ref == 0 else "{:.3f}".format(err / ref)))
 
 
-def log_ratio(name, ratio):
-    """With DORKNET_SLACK_LOG=<file>: append "dw<TAB>name<TAB>worst err / bound" for a per-element check
-    (tests/_dw_ref.py:check) -- a recorded result, not a tolerance; log_slack's lines are the normwise tests'."""
+def log_ratio(name, ratio, tag="dw"):
+    """With DORKNET_SLACK_LOG=<file>: append "tag<TAB>name<TAB>worst err / bound" for a per-element check
+    (tests/_dw_ref.py:check; tag "dw" the depthwise, "pw" the pointwise family) -- a recorded result, not a
+    tolerance; log_slack's lines are the normwise tests'."""
     import os
     path = os.environ.get("DORKNET_SLACK_LOG")
     if path:
         with open(path, "a") as f:
-            f.write("dw\t{}\t{:.4f}\n".format(name, ratio))
+            f.write("{}\t{}\t{:.4f}\n".format(tag, name, ratio))

@@ -208,11 +208,11 @@ def worst(got, ref, bound):
     return float(ratio[k]), tuple(int(v) for v in k)
 
 
-def check(name, got, ref, bound):
-    """Assert every element within its bound; returns the worst ratio."""
+def check(name, got, ref, bound, tag="dw"):
+    """Assert every element within its bound; returns the worst ratio (logged under the family's tag)."""
     from tests._convert import log_ratio
     r, k = worst(got, ref, bound)
-    log_ratio(name, r)
+    log_ratio(name, r, tag)
     assert r <= 1.0, "{}: element {} got {!r} want {!r} bound {:.3e} (err / bound = {:.3g})".format(
         name, k, float(np.asarray(got)[k]), float(ref[k]), float(bound[k]), r)
     return r

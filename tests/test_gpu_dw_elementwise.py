@@ -40,37 +40,14 @@ import torch
 
 from dorknet_amd._hip import HipError, lib, stream_handle, workspace
 from tests import _dw_ref as D
+from tests._guard import Guarded
 
 pytestmark = pytest.mark.gpu
 
 BF16 = torch.bfloat16
 F32 = torch.float32
-MARGIN = 64
 L2 = float(np.float32(1e-3))
 GIDS = sorted(D.GEOMS)
-NAN_BITS = {F32: (torch.int32, 0x7FC0DEAD), BF16: (torch.int16, 0x7FC1)}
-
-
-class Guarded:
-    """An output of `shape` (NHWC or flat) inside a NaN-filled allocation with sentinel margins."""
-
-    def __init__(self, shape, dtype):
-        self.shape, self.n = shape, int(np.prod(shape))
-        self.itype, self.bits = NAN_BITS[dtype]
-        self.buf = torch.empty(self.n + 2 * MARGIN, dtype=dtype, device="cuda")
-        self.buf.view(self.itype).fill_(self.bits)
-        self.ptr = self.buf.data_ptr() + MARGIN * self.buf.element_size()
-        assert self.ptr % 16 == 0
-
-    def result(self):
-        """The output as fp64 on the host, after the margin and NaN checks."""
-        torch.cuda.synchronize()
-        ints = self.buf.view(self.itype).cpu()
-        assert bool((ints[:MARGIN] == self.bits).all()), "store before the output"
-        assert bool((ints[MARGIN + self.n:] == self.bits).all()), "store past the output"
-        out = self.buf[MARGIN:MARGIN + self.n].double().cpu().numpy().reshape(self.shape)
-        assert not np.isnan(out).any(), "{} elements never written".format(int(np.isnan(out).sum()))
-        return out
 
 
 def nchw(a):

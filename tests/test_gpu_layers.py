@@ -148,6 +148,9 @@ PW_CASES = [
     (512, 512, 1, 4, 7, 7, False, 1e-4),    # res8 pw
     (16, 3, 1, 2, 9, 7, True, 1e-4),        # C % 4 != 0: zero-padded channels (the reference takes any C)
     (8, 6, 2, 3, 10, 10, False, 1e-4),      # C % 4 != 0 with stride 2 + widen
+    (64, 128, 1, 3, 13, 11, False, 1e-4),   # 429 pixels: ragged for 32-, 64- and 128-pixel tiles
+    (256, 128, 1, 1, 1, 33, False, 1e-4),   # deep kernels: one full 32-pixel tile plus one pixel
+    (128, 128, 2, 2, 13, 9, False, 1e-4),   # stride 2 on odd H and W: the widened grid is larger than the input
 ]
 
 

@@ -3,8 +3,9 @@ input BN's backward partials in one pass) against the unfused sequence the netwo
 dk_pwconv_dgrad_bnbwd_f32 (which forms and stores dy) and dk_pwconv_wgrad_bnx_f32 on that dy.
 dx is bit-identical (same dy values, same k-ordered MFMA chain, same residual add); the weight
 gradient and the input BN's partial sums are fixed-order reductions grouped differently, so
-they agree to fp32 / fp64 rounding.  Parity of the unfused sequence with the fp64 oracle is
-covered in test_gpu_layers.py / test_gpu_network.py."""
+they agree to fp32 / fp64 rounding.  Parity with the fp64 oracle: per element, of both the fused
+entry point and the unfused sequence, in test_gpu_pw_elementwise.py; normwise through the layers in
+test_gpu_layers.py / test_gpu_network.py."""
 import numpy as np
 import pytest
 import torch

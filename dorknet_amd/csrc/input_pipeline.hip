@@ -13,6 +13,9 @@
 //   mixup    X_mixed = p * X_m + (1 - p) * X and its mirror, for images and one-hot labels,
 //            with p and 1 - p rounded to fp32 first as numpy does for a Python float times a
 //            float32 array.  Exact.
+//   augment  data_loading/image_augmentation.py:16-72: HSV perturbation, rotation, translation and
+//            flip of a uint8 BGR batch in one pass, to uint8 NHWC or straight to fp32 NCHW (the cast
+//            fused in); see augment_u8_kernel.  Bit-exact to tests/_augment_ref.py.
 #include "dk_common.h"
 
 // Built with -ffp-contract=off (__graft_entry__.EXTRA_FLAGS): every fp32 / fp64 operation is
@@ -137,6 +140,165 @@ __global__ void mixup_kernel(const float* __restrict__ a, const float* __restric
   ba[i] = __fadd_rn(__fmul_rn(p, x), __fmul_rn(q, y));  // p * X + (1 - p) * X_m
 }
 
+// Image augmentation (data_loading/image_augmentation.py:16-72), all four steps of the reference in one
+// pass over a uint8 BGR batch; tests/_augment_ref.py restates them one after the other and pins this bit
+// for bit.  For output pixel (y, x) of image n:
+//   flip         x1 = flip ? W - 1 - x : x                       (im[:, ::-1, :], the last step)
+//   translation  (x2, y2) = (x1 - tx, y - ty), 0 outside         (warpAffine by whole pixels: an exact
+//                                                                 shifted copy with zero fill)
+//   rotation     cv2.warpAffine INTER_LINEAR / BORDER_CONSTANT 0 at (x2, y2): the inverse matrix m (formed
+//                on the host in double), X = (cvRound((m1 y + m2) 1024) + 16 + cvRound(m0 x 1024)) >> 5,
+//                sx = X >> 5, fx = X & 31 (likewise Y), four taps weighted (32 - fx)(32 - fy) 32 ...,
+//                (sum + 2^14) >> 15; a tap outside the image is 0
+//   HSV          every tap inside the image is the perturbed source pixel: cvtColor BGR2HSV (uint8,
+//                integer, hue range 180), three fp32 factors, clip, truncate, cvtColor HSV2BGR (fp32,
+//                one rounding per operation: this file is built with -ffp-contract=off)
+// One thread per output pixel, its three channels together: a wave writes 192 adjacent bytes (uint8
+// NHWC out) or 256 adjacent bytes per channel plane (fp32 NCHW out).  The source is a crop window
+// rows x cols at (row, col) of an H x W image, so the pipeline needs no crop copy.  blockIdx.y is the
+// image (its parameters are uniform over a block), blockIdx.x * 256 + threadIdx.x the pixel within it.
+struct AugParams {   // = dk_augment_params
+  double m[6];
+  float hsv[3];
+  int tx, ty, flags;
+};
+static_assert(sizeof(AugParams) == sizeof(dk_augment_params), "parameter record layout");
+enum : int { AUG_HSV = 1, AUG_ROTATE = 2, AUG_FLIP = 4 };
+
+struct Bgr {
+  int b, g, r;
+};
+
+// n / den rounded half to even (cvRound of the quotient: a tie is exact in double too)
+__device__ __forceinline__ int div_round_even(int n, int den) {
+  const int q = n / den, rem = n - q * den;
+  return q + ((2 * rem > den || (2 * rem == den && (q & 1))) ? 1 : 0);
+}
+
+__device__ __forceinline__ float pick4(int k, float t0, float t1, float t2, float t3) {
+  return k == 0 ? t0 : k == 1 ? t1 : k == 2 ? t2 : t3;
+}
+
+__device__ __forceinline__ int cv_sat_u8(float v) { return min(max((int)rintf(v), 0), 255); }
+
+__device__ __forceinline__ Bgr hsv_perturb(Bgr p, const int* sdiv, const int* hdiv, float fh, float fs, float fv) {
+  // BGR -> HSV, uint8
+  const int v = max(max(p.b, p.g), p.r), vmin = min(min(p.b, p.g), p.r), d = v - vmin;
+  const int s = (d * sdiv[v] + 2048) >> 12;
+  const int h0 = v == p.r ? p.g - p.b : v == p.g ? p.b - p.r + 2 * d : p.r - p.g + 4 * d;
+  int h = (h0 * hdiv[d] + 2048) >> 12;
+  if (h < 0) h += 180;
+  // scale in fp32, clip, truncate to uint8
+  const int hi = (int)fminf(fminf(fmaxf(__fmul_rn((float)h, fh), 0.f), 255.f), 179.f);
+  const int si = (int)fminf(fmaxf(__fmul_rn((float)s, fs), 0.f), 255.f);
+  const int vi = (int)fminf(fmaxf(__fmul_rn((float)v, fv), 0.f), 255.f);
+  // HSV -> BGR, fp32
+  const float hf = __fmul_rn((float)hi, 6.f / 180.f), sf = __fmul_rn((float)si, 1.f / 255.f),
+              vf = __fmul_rn((float)vi, 1.f / 255.f);
+  float b = vf, g = vf, r = vf;
+  if (si != 0) {
+    const float sec = floorf(hf);
+    float f = __fsub_rn(hf, sec);
+    int k = (int)sec;
+    if (k < 0 || k > 5) {
+      k = 0;
+      f = 0.f;
+    }
+    const float t0 = vf, t1 = __fmul_rn(vf, __fsub_rn(1.f, sf)), t2 = __fmul_rn(vf, __fsub_rn(1.f, __fmul_rn(sf, f))),
+                t3 = __fmul_rn(vf, __fsub_rn(1.f, __fmul_rn(sf, __fsub_rn(1.f, f))));
+    // (b, g, r) = tab[{1,3,0}, {1,0,2}, {3,0,1}, {0,2,1}, {0,1,3}, {2,1,0}][sector], two bits per sector
+    const int sh = 2 * k;
+    const int bsel = 1 | 1 << 2 | 3 << 4 | 0 << 6 | 0 << 8 | 2 << 10;
+    const int gsel = 3 | 0 << 2 | 0 << 4 | 2 << 6 | 1 << 8 | 1 << 10;
+    const int rsel = 0 | 2 << 2 | 1 << 4 | 1 << 6 | 3 << 8 | 0 << 10;
+    b = pick4((bsel >> sh) & 3, t0, t1, t2, t3);
+    g = pick4((gsel >> sh) & 3, t0, t1, t2, t3);
+    r = pick4((rsel >> sh) & 3, t0, t1, t2, t3);
+  }
+  Bgr o;
+  o.b = cv_sat_u8(__fmul_rn(b, 255.f));
+  o.g = cv_sat_u8(__fmul_rn(g, 255.f));
+  o.r = cv_sat_u8(__fmul_rn(r, 255.f));
+  return o;
+}
+
+// cvRound to a 64-bit integer, clamped far outside any image (a NaN takes the low end)
+__device__ __forceinline__ long long round_fix(double v) {
+  const double lim = 1099511627776.0;  // 2^40
+  return (long long)fmin(fmax(rint(v), -lim), lim);
+}
+
+template <bool F32>
+__global__ __launch_bounds__(256) void augment_u8_kernel(const uint8_t* __restrict__ src, int N, int H, int W,
+                                                         const int* __restrict__ crop, int rows, int cols,
+                                                         const AugParams* __restrict__ params, float shift,
+                                                         void* __restrict__ dst) {
+  // the two division tables of BGR2HSV: sdiv[i] = cvRound((255 << 12) / i), hdiv[i] = cvRound((180 << 12) / 6 i)
+  __shared__ int sdiv[256], hdiv[256];
+  {
+    const int t = threadIdx.x;  // blockDim.x == 256
+    sdiv[t] = t ? div_round_even(255 << 12, t) : 0;
+    hdiv[t] = t ? div_round_even(180 << 12, 6 * t) : 0;
+  }
+  __syncthreads();
+  const int n = blockIdx.y;
+  const int i = blockIdx.x * 256 + threadIdx.x;  // over rows * cols (< 2^31 - 256: the entry points check)
+  if (n >= N || i >= rows * cols) return;
+  const int x = i % cols, y = i / cols;
+  const AugParams& P = params[n];
+  const int flags = P.flags;
+  const float fh = P.hsv[0], fs = P.hsv[1], fv = P.hsv[2];
+  // offsets clamped into the image (a bad offset cannot read out of bounds)
+  const int r0 = crop ? min(max(crop[2 * n], 0), H - rows) : 0, c0 = crop ? min(max(crop[2 * n + 1], 0), W - cols) : 0;
+  const uint8_t* im = src + (((size_t)n * H + r0) * W + c0) * 3;
+  const size_t pitch = (size_t)W * 3;
+
+  // the (perturbed) source pixel at (yy, xx) of the window, 0 outside it
+  auto tap = [&](long long yy, long long xx) {
+    Bgr p = {0, 0, 0};
+    if (yy >= 0 && yy < rows && xx >= 0 && xx < cols) {
+      const uint8_t* q = im + (size_t)yy * pitch + (size_t)xx * 3;
+      p.b = q[0];
+      p.g = q[1];
+      p.r = q[2];
+      if (flags & AUG_HSV) p = hsv_perturb(p, sdiv, hdiv, fh, fs, fv);
+    }
+    return p;
+  };
+
+  const long long x2 = (long long)((flags & AUG_FLIP) ? cols - 1 - x : x) - P.tx, y2 = (long long)y - P.ty;
+  Bgr o = {0, 0, 0};
+  if (x2 >= 0 && x2 < cols && y2 >= 0 && y2 < rows) {
+    if (flags & AUG_ROTATE) {
+      const double xd = (double)x2, yd = (double)y2;
+      const long long X = (round_fix((P.m[1] * yd + P.m[2]) * 1024.0) + 16 + round_fix(P.m[0] * xd * 1024.0)) >> 5;
+      const long long Y = (round_fix((P.m[4] * yd + P.m[5]) * 1024.0) + 16 + round_fix(P.m[3] * xd * 1024.0)) >> 5;
+      // clamped next to the window: a tap that far out is 0 either way
+      const long long sx = min(max(X >> 5, -2LL), (long long)cols), sy = min(max(Y >> 5, -2LL), (long long)rows);
+      const int fx = (int)(X & 31), fy = (int)(Y & 31);
+      const Bgr a = tap(sy, sx), b = tap(sy, sx + 1), c = tap(sy + 1, sx), d = tap(sy + 1, sx + 1);
+      const int wa = (32 - fx) * (32 - fy) * 32, wb = fx * (32 - fy) * 32, wc = (32 - fx) * fy * 32, wd = fx * fy * 32;
+      o.b = (a.b * wa + b.b * wb + c.b * wc + d.b * wd + 16384) >> 15;
+      o.g = (a.g * wa + b.g * wb + c.g * wc + d.g * wd + 16384) >> 15;
+      o.r = (a.r * wa + b.r * wb + c.r * wc + d.r * wd + 16384) >> 15;
+    } else {
+      o = tap(y2, x2);
+    }
+  }
+  if constexpr (F32) {
+    float* out = (float*)dst + ((size_t)n * 3 * rows + y) * cols + x;  // NCHW
+    const size_t plane = (size_t)rows * cols;
+    out[0] = __fsub_rn((float)o.b, shift);
+    out[plane] = __fsub_rn((float)o.g, shift);
+    out[2 * plane] = __fsub_rn((float)o.r, shift);
+  } else {
+    uint8_t* out = (uint8_t*)dst + ((size_t)n * rows * cols + i) * 3;  // NHWC
+    out[0] = (uint8_t)o.b;
+    out[1] = (uint8_t)o.g;
+    out[2] = (uint8_t)o.r;
+  }
+}
+
 }  // namespace dk
 
 using namespace dk;
@@ -172,4 +334,38 @@ DK_API int dk_mixup_f32(const float* a, const float* b, long long n, float p, fl
   hipLaunchKernelGGL(mixup_kernel, dim3(blocks256(n)), dim3(256), 0, as_stream(stream), a, b, n, p, one_minus_p, ab,
                      ba);
   return launch_status();
+}
+
+static inline bool augment_args_ok(const void* src, int N, int H, int W, int C, int OH, int OW, const void* params,
+                                   const void* dst) {
+  return src && dst && params && N >= 1 && C == 3 && OH >= 1 && OW >= 1 && OH <= H && OW <= W &&
+         (long long)OH * OW <= 0x7fffffffLL - 256;  // the kernel's 32-bit pixel index
+}
+
+// grid.y is the image (at most 65535 per launch: larger batches take several launches)
+template <bool F32>
+static int launch_augment(const uint8_t* src, int N, int H, int W, const int* crop_rc, int OH, int OW,
+                          const dk_augment_params* params, float shift, void* dst, void* stream) {
+  const int kMaxY = 65535;
+  const size_t out_image = (size_t)OH * OW * 3 * (F32 ? sizeof(float) : 1);
+  for (int n0 = 0; n0 < N; n0 += kMaxY) {
+    const int nb = N - n0 < kMaxY ? N - n0 : kMaxY;
+    hipLaunchKernelGGL(augment_u8_kernel<F32>, dim3(blocks256((long long)OH * OW), nb), dim3(256), 0, as_stream(stream),
+                       src + (size_t)n0 * H * W * 3, nb, H, W, crop_rc ? crop_rc + 2 * (size_t)n0 : nullptr, OH, OW,
+                       reinterpret_cast<const AugParams*>(params) + n0, shift,
+                       (void*)((uint8_t*)dst + (size_t)n0 * out_image));
+  }
+  return launch_status();
+}
+
+DK_API int dk_augment_u8(const uint8_t* src, int N, int H, int W, int C, const int* crop_rc, int OH, int OW,
+                         const dk_augment_params* params, uint8_t* dst, void* stream) {
+  if (!augment_args_ok(src, N, H, W, C, OH, OW, params, dst)) return DK_ERR_ARGS;
+  return launch_augment<false>(src, N, H, W, crop_rc, OH, OW, params, 0.f, dst, stream);
+}
+
+DK_API int dk_augment_u8_to_nchw_f32(const uint8_t* src, int N, int H, int W, int C, const int* crop_rc, int OH, int OW,
+                                     const dk_augment_params* params, float shift, float* dst, void* stream) {
+  if (!augment_args_ok(src, N, H, W, C, OH, OW, params, dst)) return DK_ERR_ARGS;
+  return launch_augment<true>(src, N, H, W, crop_rc, OH, OW, params, shift, dst, stream);
 }

@@ -47,6 +47,32 @@ int dk_resize_bilinear_u8(const uint8_t* src, int N, int H, int W, int C, int OH
 int dk_u8_nhwc_to_nchw_f32(const uint8_t* src, int N, int H, int W, int C, const int* crop_rc, int OH, int OW, float shift, float* dst, void* stream);
 int dk_mixup_f32(const float* a, const float* b, long long n, float p, float one_minus_p, float* ab, float* ba, void* stream);
 
+/* Image augmentation for a uint8 BGR batch (C = 3), replacing ImageAugmenter.augment
+ * (data_loading/image_augmentation.py:16-72): HSV perturbation (cvtColor BGR2HSV, three fp32 factors,
+ * clip, cvtColor HSV2BGR), rotation (warpAffine, INTER_LINEAR, constant border 0), translation by whole
+ * pixels and horizontal flip, in that order, in one pass (OpenCV 4.3 restated,
+ * pinned bit for bit by tests/_augment_ref.py).
+ * The source is the OH x OW window at crop_rc[n] = (row, col) of each H x W image (device int32 [N][2];
+ * NULL: 0, 0; offsets clamped into the image), so a crop needs no copy; the transforms act on the window.
+ * params: device array of N records:
+ *   m      the INVERSE rotation map as cv2.warpAffine forms it in double (row-major 2x3), used with flag 2;
+ *   hsv    the hue, saturation and value factors, used with flag 1;
+ *   tx, ty whole-pixel shift of columns / rows (0, 0: none);
+ *   flags  1: HSV perturbation, 2: rotation, 4: horizontal flip.
+ *  - dk_augment_u8: dst uint8 NHWC [N][OH][OW][3];
+ *  - dk_augment_u8_to_nchw_f32: dst fp32 NCHW [N][3][OH][OW], each value minus shift (the cast of
+ *    dk_u8_nhwc_to_nchw_f32 fused in).
+ * C != 3, a NULL src / params / dst or a window larger than the image: 10001, nothing is launched. */
+typedef struct dk_augment_params {
+  double m[6];
+  float hsv[3];
+  int tx;
+  int ty;
+  int flags;
+} dk_augment_params;
+int dk_augment_u8(const uint8_t* src, int N, int H, int W, int C, const int* crop_rc, int OH, int OW, const dk_augment_params* params, uint8_t* dst, void* stream);
+int dk_augment_u8_to_nchw_f32(const uint8_t* src, int N, int H, int W, int C, const int* crop_rc, int OH, int OW, const dk_augment_params* params, float shift, float* dst, void* stream);
+
 /* Path selectors and tuning knobs for tests and A/B runs (dorknet_amd/csrc/knobs.hip: one registry
  * of atomics holding built-in defaults; no environment variable reaches them; not for production
  * use).  cfg = -1 restores the default.  Returns the number of configurations for kinds 0 / 1, 0 for

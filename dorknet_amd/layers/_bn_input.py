@@ -98,6 +98,38 @@ class BNOut:
         return self._y
 
 
+NO_BN = (0, 0, 0, 0, 0)  # bn_args() of an input that is no BNOut
+
+
+def bn_args(bn):
+    """(mean, invstd, gamma, beta, relu) of the BNOut a launch applies on load, NO_BN without one."""
+    return bn.bn_args() if bn is not None else NO_BN
+
+
+class Partials:
+    """Stage 1 of `bn`'s backward, written by a consumer's backward launch (`bn`: the BNOut that
+    launch produces the gradient of).  Built immediately before the launch: allocates the fp64
+    [rows, 2, C] buffer and arms the in-launch fold on it (arm_partials); the launch takes `ptr`;
+    hand(dx, status) passes buffer and gradient on to the BatchNorm (hand_backward_partials, which
+    drops the arming when the launch did not fold).  Without a BNOut: a null pointer, hand() a no-op."""
+    __slots__ = ("bn", "part", "token")
+
+    def __init__(self, bn, rows, C, device):
+        self.bn = bn
+        self.part = self.token = None
+        if bn is not None:
+            self.part = torch.empty((rows, 2, C), dtype=torch.float64, device=device)
+            self.token = bn.arm_partials(self.part)
+
+    @property
+    def ptr(self):
+        return 0 if self.part is None else self.part.data_ptr()
+
+    def hand(self, dx, status):
+        if self.bn is not None:
+            self.bn.hand_backward_partials(dx, self.part, status, self.token)
+
+
 class JoinOut:
     """A residual block's output y = ReLU(bnA(a) + bnB(b)) (residual_block.py:75) not yet written.
 
@@ -295,6 +327,24 @@ def residual_operand(residual, like):
             like.shape) and r.dim() == 4 and is_nhwc(r):
         return r
     return None
+
+
+def fused_residual(residual, dx, lattice=0, retry=True):
+    """`residual` as the addend of the dgrad that writes `dx`: (residual, operand, s).  With
+    `lattice` >= 2 a residual handed over as that compact lattice is the operand as it is
+    (s = lattice).  Otherwise (s = 0) the residual is widened to dx's grid (dense_residual) and the
+    operand is that tensor if it is NHWC of dx's type, with `retry` its to_nhwc copy if that is,
+    else None: the caller then adds the returned residual itself (add_residual)."""
+    if residual is None:
+        return None, None, 0
+    lat = lattice_operand(residual, dx, lattice)
+    if lat is not None:
+        return residual, lat, lattice
+    residual = dense_residual(residual, dx.shape)
+    res = residual_operand(residual, dx)
+    if res is None and retry:
+        res = residual_operand(to_nhwc(residual), dx)
+    return residual, res, 0
 
 
 def add_residual(dx, residual):

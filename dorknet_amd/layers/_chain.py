@@ -17,6 +17,8 @@ the per-layer parity tests; results are bit-identical either way).
 """
 from __future__ import annotations
 
+import torch
+
 from .._env import enabled
 from .._hip import (DK_FOLDED, disarm_folds, early_flush_steps, flush_wgrad_reduces, inlaunch_folds_enabled,
                     inline_wgrad_reduces, lib, resolve)
@@ -95,7 +97,7 @@ class StatsRequest:
     BatchNormLayer that follows then skips its own statistics pass.
 
     With ``bn`` (the BatchNormLayer that will consume them) the producer also arms an in-launch
-    fold (``arm`` before its launch, ``launched`` after it; dorknet_amd/csrc/fold_tail.h): the
+    fold (``arm_buffer`` before its launch, ``launched`` after it; dorknet_amd/csrc/fold_tail.h): the
     producer's last blocks then finalize the statistics themselves and the BatchNormLayer skips
     the fold launch too."""
     __slots__ = ("part", "rows", "bn", "armed", "folded")
@@ -107,11 +109,14 @@ class StatsRequest:
         self.armed = None   # (mean, std, invstd) the armed fold will write
         self.folded = None  # the same, once the producer's launch has folded
 
-    def arm(self, part, P):
-        """Before the producer's launch: `part` [rows, 2, C] will hold its partial sums over P
-        pixels per channel."""
+    def arm_buffer(self, rows, K, device, P):
+        """Immediately before the producer's launch: the fp64 [rows, 2, K] buffer that will hold its
+        partial sums over P pixels per channel, armed; the launch takes its pointer, `launched` the
+        buffer and the launch's status."""
+        part = torch.empty((rows, 2, K), dtype=torch.float64, device=device)
         if self.bn is not None and inlaunch_folds_enabled():
             self.armed = self.bn.arm_stats_fold(part, P)
+        return part
 
     def launched(self, part, status):
         """After the producer's launch (`status`: the entry point's return value)."""

@@ -4,7 +4,7 @@ from __future__ import annotations
 import numpy as np
 import torch
 
-from .._hip import lib, stream_handle
+from .._hip import lib, stream_handle, weight_grad_stream, workspace
 from .._tensor import as_device
 
 
@@ -43,6 +43,27 @@ def grad_buffer(layer, key: str, shape) -> torch.Tensor:
         layer.grads[key] = g
     cache[key] = (g, shape)
     return g
+
+
+def weight_grad(layer, dy, x, P, K, shape, launch, colsum="dk_colsum_f32"):
+    """The frame around a layer's weight-gradient launch, on the side stream
+    (_hip.weight_grad_stream): the bias gradient (the column sums of dy as [P, K], `colsum`), then
+    launch(w, strength, gw, stream) -- w / strength: the weights and the l2 strength the kernel
+    folds in (0 / 0.0 without an l2 regulariser), gw: grads["weights"] of `shape` -- and any other
+    regulariser's term added to gw after it.  The launch takes its workspace inside (workspace.get
+    is per stream)."""
+    w = layer.learned_params["weights"]
+    with weight_grad_stream(dy, x, *layer._bn_tensors()):
+        sst = stream_handle()
+        if layer.with_bias:
+            gb = grad_buffer(layer, "bias", (K,))
+            nb = lib.dk_colsum_workspace_bytes(P, K)
+            getattr(lib, colsum)(dy.data_ptr(), P, K, gb.data_ptr(), workspace.get(nb), nb, sst)
+        gw = grad_buffer(layer, "weights", shape)
+        s = l2_strength(layer.weight_regulariser)
+        launch(w.data_ptr() if s else 0, s or 0.0, gw.data_ptr(), sst)
+        if s is None:
+            add_regulariser_grad(gw, w, layer.weight_regulariser)
 
 
 def init_weights(shape, initialiser: str, fan_sum: float) -> np.ndarray:

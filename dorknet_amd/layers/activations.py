@@ -12,7 +12,7 @@ import torch
 
 from .._hip import lib, stream_handle
 from .._tensor import act_dtype, as_device, empty_nhwc, is_nhwc as is_nhwc_t, rows, to_nhwc
-from ._bn_input import BNOut, JoinOut
+from ._bn_input import BNOut, JoinOut, Partials
 from .layer import Layer
 
 
@@ -200,12 +200,11 @@ class ReLu(Layer):
             C = dy.shape[1]
             P = dy.numel() // C
             nb = lib.dk_bn_workspace_bytes(P, C)
-            part = torch.empty((lib.dk_bn_partial_blocks(P, C), 2, C), dtype=torch.float64, device=dy.device)
-            tok = bn.arm_partials(part)
+            part = Partials(bn, lib.dk_bn_partial_blocks(P, C), C, dy.device)
             bwd = lib.dk_relu_bwd_bn_partial_bf16 if _bf16(dy, bn.x) else lib.dk_relu_bwd_bn_partial_f64
             r = bwd(dy.data_ptr(), self._mask.data_ptr(), bn.x.data_ptr(), P, C, *bn.bn_args(), dx.data_ptr(),
-                    part.data_ptr(), nb, stream_handle())
-            bn.hand_backward_partials(dx, part, r, tok)
+                    part.ptr, nb, stream_handle())
+            part.hand(dx, r)
             return dx
         bwd = lib.dk_relu_bwd_bf16 if dy.dtype == torch.bfloat16 else lib.dk_relu_bwd_f32
         bwd(dy.data_ptr(), self._mask.data_ptr(), dy.numel(), dx.data_ptr(), stream_handle())

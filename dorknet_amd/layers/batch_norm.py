@@ -26,6 +26,10 @@ from ._bn_input import BNGrad, BNOut, widen_lattice
 from ._common import grad_buffer
 from .layer import Layer
 
+# per storage type: the one-launch backward, and the last stage of the staged one
+_BWD = {torch.float32: "dk_bn_bwd_f32", BF16: "dk_bn_bwd_bf16"}
+_BWD_APPLY = {torch.float32: "dk_bn_bwd_apply_f32", BF16: "dk_bn_bwd_apply_bf16"}
+
 
 class BatchNormLayer(Layer):
     """
@@ -303,12 +307,12 @@ class BatchNormLayer(Layer):
                                            dgamma.data_ptr(), dbeta.data_ptr(), k12.data_ptr(), st)
             if defer:
                 return BNGrad(dy, x, self._mean, self._invstd, gamma, beta, relu, k12, lattice=lattice)
-            (lib.dk_bn_bwd_apply_bf16 if bf else lib.dk_bn_bwd_apply_f32)(
+            getattr(lib, _BWD_APPLY[x.dtype])(
                 x.data_ptr(), dy.data_ptr(), x.numel(), C, self._mean.data_ptr(), self._invstd.data_ptr(),
                 gamma.data_ptr(), beta.data_ptr(), int(relu), k12.data_ptr(), dx.data_ptr(), st)
         elif self.sync_group is None:
             nb = lib.dk_bn_bwd_workspace_bytes(P, C)
-            (lib.dk_bn_bwd_bf16 if bf else lib.dk_bn_bwd_f32)(
+            getattr(lib, _BWD[x.dtype])(
                 x.data_ptr(), dy.data_ptr(), P, C, self._mean.data_ptr(), self._invstd.data_ptr(), gamma.data_ptr(),
                 beta.data_ptr(), int(relu), dgamma.data_ptr(), dbeta.data_ptr(), dx.data_ptr(), workspace.get(nb), nb,
                 st)
@@ -330,7 +334,7 @@ class BatchNormLayer(Layer):
                                        dgamma.data_ptr(), dbeta.data_ptr(), k12.data_ptr(), st)
             if defer and not bf:
                 return BNGrad(dy, x, self._mean, self._invstd, gamma, beta, relu, k12)
-            (lib.dk_bn_bwd_apply_bf16 if bf else lib.dk_bn_bwd_apply_f32)(
+            getattr(lib, _BWD_APPLY[x.dtype])(
                 x.data_ptr(), dy.data_ptr(), x.numel(), C, self._mean.data_ptr(), self._invstd.data_ptr(),
                 gamma.data_ptr(), beta.data_ptr(), int(relu), k12.data_ptr(), dx.data_ptr(), st)
         return dx

@@ -23,11 +23,21 @@ from __future__ import annotations
 import torch
 
 from .._env import getenv
-from .._hip import lib, stream_handle, weight_grad_stream, workspace
+from .._hip import lib, stream_handle, workspace
 from .._tensor import BF16, as_device, empty_nhwc, ptr, to_nhwc
-from ._bn_input import BNGrad, BNOut
-from ._common import add_regulariser_grad, grad_buffer, init_weights, l2_strength
+from ._bn_input import BNGrad, BNOut, bn_args
+from ._common import add_regulariser_grad, grad_buffer, init_weights, l2_strength, weight_grad
 from .layer import Layer
+
+# Per storage type, the entry points with the queries that belong to them (names: resolved on
+# `lib` at the call).  Forward: (the _ex entry, its statistics-row query).
+_FWD_EX = {torch.float32: ("dk_conv2d_fwd_ex_f32", "dk_conv2d_fwd_stats_rows"),
+           BF16: ("dk_conv2d_fwd_ex_bf16", "dk_conv2d_fwd_bf16_stats_rows")}
+# Weight gradient: (plain entry, BatchNorm-on-load entry, their workspace query, the bias column sum)
+_WGRAD = {torch.float32: ("dk_conv2d_wgrad_f32", "dk_conv2d_wgrad_bnx_f32", "dk_conv2d_wgrad_workspace_bytes",
+                          "dk_colsum_f32"),
+          BF16: ("dk_conv2d_wgrad_bf16", "dk_conv2d_wgrad_bnx_bf16", "dk_conv2d_wgrad_bf16_workspace_bytes",
+                 "dk_colsum_bf16")}
 
 
 class ConvLayer(Layer):
@@ -102,15 +112,12 @@ class ConvLayer(Layer):
         stats = None
         if bn_stats is not None and not test_mode:
             rows = lib.dk_conv2d_fwd_narrow_stats_rows(N, C, H, W, K, R, S, self.stride, self.padding, OH, OW)
-            stats = torch.empty((rows, 2, K), dtype=torch.float64, device=x.device)
-            bn_stats.arm(stats, N * OH * OW)
+            stats = bn_stats.arm_buffer(rows, K, x.device, N * OH * OW)
         r = lib.dk_conv2d_fwd_narrow_f32(x.data_ptr(), N, C, H, W, self.learned_params["weights"].data_ptr(), K, R,
                                          S, self.stride, self.padding, ptr(bias), y.data_ptr(), OH, OW, ptr(stats),
                                          st)
         if stats is not None:
             bn_stats.launched(stats, r)
-        elif r:
-            raise RuntimeError(f"dk_conv2d_fwd_narrow_f32 failed: {r}")
         self.X = x
         self._bn_in = None
         self._narrow = True
@@ -137,18 +144,14 @@ class ConvLayer(Layer):
         lib.dk_conv_weight_krsc_f32(w.data_ptr(), K, C, R, S, Cp, w_krsc.data_ptr(), st)
         y = empty_nhwc(N, K, OH, OW, x.dtype)
         bias = self.learned_params["bias"] if self.with_bias else None
-        stats = None
-        if bn_stats is not None and not test_mode:
-            rows = (lib.dk_conv2d_fwd_bf16_stats_rows if bf else lib.dk_conv2d_fwd_stats_rows)(N, OH, OW, K, Cp, R, S)
-            stats = torch.empty((rows, 2, K), dtype=torch.float64, device=x.device)
-        if bn is not None or stats is not None or bf:
-            fwd = lib.dk_conv2d_fwd_ex_bf16 if bf else lib.dk_conv2d_fwd_ex_f32
-            if stats is not None:
-                bn_stats.arm(stats, N * OH * OW)
-            r = fwd(x.data_ptr(), N, H, W, Cp, w_krsc.data_ptr(), K, R, S, self.stride,
-                    self.padding, ptr(bias), y.data_ptr(), OH, OW,
-                    *(bn.bn_args() if bn is not None else (0, 0, 0, 0, 0)), ptr(stats), st)
-            if stats is not None:
+        want_stats = bn_stats is not None and not test_mode
+        if bn is not None or want_stats or bf:
+            entry, rows_query = _FWD_EX[x.dtype]
+            stats = (bn_stats.arm_buffer(getattr(lib, rows_query)(N, OH, OW, K, Cp, R, S), K, x.device, N * OH * OW)
+                     if want_stats else None)
+            r = getattr(lib, entry)(x.data_ptr(), N, H, W, Cp, w_krsc.data_ptr(), K, R, S, self.stride, self.padding,
+                                    ptr(bias), y.data_ptr(), OH, OW, *bn_args(bn), ptr(stats), st)
+            if want_stats:
                 bn_stats.launched(stats, r)
         else:
             lib.dk_conv2d_fwd_f32(x.data_ptr(), N, H, W, Cp, w_krsc.data_ptr(), K, R, S, self.stride, self.padding,
@@ -193,23 +196,45 @@ class ConvLayer(Layer):
             lat = G.lattice if G.lattice == 2 else 1
             g = G.g_compact if lat == 2 else to_nhwc(G.g)
             nb = lib.dk_conv2d_wgrad_narrow_workspace_bytes(N, Cp, H, W, K, R, S, self.stride, self.padding, OH, OW)
-            r = lib.dk_conv2d_wgrad_bnbwd_narrow_f32(g.data_ptr(), G.x.data_ptr(), x.data_ptr(), N, Cp, H, W, K, R, S,
-                                                     self.stride, self.padding, OH, OW, *G.bnbwd_args(), lat,
-                                                     w.data_ptr() if s else 0, s or 0.0, gw.data_ptr(),
-                                                     workspace.get(nb), nb, st)
-            if r:
-                raise RuntimeError(f"dk_conv2d_wgrad_bnbwd_narrow_f32 failed: {r}")
-            if s is None:
-                add_regulariser_grad(gw, w, self.weight_regulariser)
-            return
-        g = to_nhwc(G.g)
-        nb = lib.dk_conv2d_wgrad_workspace_bytes(N, OH, OW, K, Cp, R, S)
-        lib.dk_conv2d_wgrad_bnbwd_f32(g.data_ptr(), G.x.data_ptr(), x.data_ptr(), N, H, W, Cp, C, K, R, S,
-                                      self.stride, self.padding, OH, OW, *G.bnbwd_args(), w.data_ptr() if s else 0,
-                                      s or 0.0, gw.data_ptr(), workspace.get(nb), nb,
-                                      *(self._bn_in.bn_args() if self._bn_in is not None else (0, 0, 0, 0, 0)), st)
+            lib.dk_conv2d_wgrad_bnbwd_narrow_f32(g.data_ptr(), G.x.data_ptr(), x.data_ptr(), N, Cp, H, W, K, R, S,
+                                                 self.stride, self.padding, OH, OW, *G.bnbwd_args(), lat,
+                                                 w.data_ptr() if s else 0, s or 0.0, gw.data_ptr(),
+                                                 workspace.get(nb), nb, st)
+        else:
+            g = to_nhwc(G.g)
+            nb = lib.dk_conv2d_wgrad_workspace_bytes(N, OH, OW, K, Cp, R, S)
+            lib.dk_conv2d_wgrad_bnbwd_f32(g.data_ptr(), G.x.data_ptr(), x.data_ptr(), N, H, W, Cp, C, K, R, S,
+                                          self.stride, self.padding, OH, OW, *G.bnbwd_args(),
+                                          w.data_ptr() if s else 0, s or 0.0, gw.data_ptr(), workspace.get(nb), nb,
+                                          *bn_args(self._bn_in), st)
         if s is None:
             add_regulariser_grad(gw, w, self.weight_regulariser)
+
+    def _wgrad(self, dy):
+        """Bias and weight gradient (+ l2 folded in, convolution.py:93-100) from dy, fp32 or bf16."""
+        x = self.X
+        N, Cp, H, W = x.shape
+        K, C, R, S = self.num_filters, self.filter_chans, self.f_rows, self.f_cols
+        OH, OW = int(self.num_row_patches), int(self.num_col_patches)
+        bn = self._bn_in
+        plain, bnx, ws_query, colsum = _WGRAD[x.dtype]
+        geom = (K, R, S, self.stride, self.padding, OH, OW)
+        if self._narrow:
+            nb = lib.dk_conv2d_wgrad_narrow_workspace_bytes(N, Cp, H, W, *geom)
+        else:
+            nb = getattr(lib, ws_query)(N, OH, OW, K, Cp, R, S)
+
+        def launch(wl2, s, gw, sst):
+            if self._narrow:
+                lib.dk_conv2d_wgrad_narrow_f32(dy.data_ptr(), x.data_ptr(), N, Cp, H, W, *geom, wl2, s, gw,
+                                               workspace.get(nb), nb, sst)
+            elif bn is not None:
+                getattr(lib, bnx)(dy.data_ptr(), x.data_ptr(), N, H, W, Cp, C, *geom, wl2, s, gw, workspace.get(nb),
+                                  nb, *bn.bn_args(), sst)
+            else:
+                getattr(lib, plain)(dy.data_ptr(), x.data_ptr(), N, H, W, Cp, C, *geom, wl2, s, gw,
+                                    workspace.get(nb), nb, sst)
+        weight_grad(self, dy, x, N * OH * OW, K, (K, C, R, S), launch, colsum)
 
     def backward(self, upstream_dx, need_dx=True):
         self._require_on_gpu()
@@ -230,37 +255,7 @@ class ConvLayer(Layer):
         K, C, R, S = self.num_filters, self.filter_chans, self.f_rows, self.f_cols
         OH, OW = int(self.num_row_patches), int(self.num_col_patches)
         w = self.learned_params["weights"]
-        P = N * OH * OW
-        # the weight gradient runs on the side stream (_hip.weight_grad_stream)
-        with weight_grad_stream(dy, x, *self._bn_tensors()):
-            sst = stream_handle()
-            if self.with_bias:
-                gb = grad_buffer(self, "bias", (K,))
-                nb = lib.dk_colsum_workspace_bytes(P, K)
-                lib.dk_colsum_f32(dy.data_ptr(), P, K, gb.data_ptr(), workspace.get(nb), nb, sst)
-            # weight gradient (+ l2 folded in, convolution.py:93-100)
-            gw = grad_buffer(self, "weights", (K, C, R, S))
-            s = l2_strength(self.weight_regulariser)
-            if self._narrow:
-                nb = lib.dk_conv2d_wgrad_narrow_workspace_bytes(N, Cp, H, W, K, R, S, self.stride, self.padding,
-                                                                OH, OW)
-                r = lib.dk_conv2d_wgrad_narrow_f32(dy.data_ptr(), x.data_ptr(), N, Cp, H, W, K, R, S, self.stride,
-                                                   self.padding, OH, OW, w.data_ptr() if s else 0, s or 0.0,
-                                                   gw.data_ptr(), workspace.get(nb), nb, sst)
-                if r:
-                    raise RuntimeError(f"dk_conv2d_wgrad_narrow_f32 failed: {r}")
-            elif self._bn_in is not None:
-                nb = lib.dk_conv2d_wgrad_workspace_bytes(N, OH, OW, K, Cp, R, S)
-                lib.dk_conv2d_wgrad_bnx_f32(dy.data_ptr(), x.data_ptr(), N, H, W, Cp, C, K, R, S, self.stride,
-                                            self.padding, OH, OW, w.data_ptr() if s else 0, s or 0.0, gw.data_ptr(),
-                                            workspace.get(nb), nb, *self._bn_in.bn_args(), sst)
-            else:
-                nb = lib.dk_conv2d_wgrad_workspace_bytes(N, OH, OW, K, Cp, R, S)
-                lib.dk_conv2d_wgrad_f32(dy.data_ptr(), x.data_ptr(), N, H, W, Cp, C, K, R, S, self.stride,
-                                        self.padding, OH, OW, w.data_ptr() if s else 0, s or 0.0, gw.data_ptr(),
-                                        workspace.get(nb), nb, sst)
-            if s is None:
-                add_regulariser_grad(gw, w, self.weight_regulariser)
+        self._wgrad(dy)
         if not need_dx:
             return None
         # input gradient (convolution.py:101-117); shape = the forward input's shape
@@ -294,29 +289,10 @@ class ConvLayer(Layer):
         K, C, R, S = self.num_filters, self.filter_chans, self.f_rows, self.f_cols
         OH, OW = int(self.num_row_patches), int(self.num_col_patches)
         w = self.learned_params["weights"]
-        P = N * OH * OW
         if tuple(dy.shape) != (N, K, OH, OW):
             raise ValueError("ConvLayer {}: gradient shape {} does not match the output {}".format(
                 self.layer_name, tuple(dy.shape), (N, K, OH, OW)))
-        with weight_grad_stream(dy, x, *self._bn_tensors()):
-            sst = stream_handle()
-            if self.with_bias:
-                gb = grad_buffer(self, "bias", (K,))
-                nb = lib.dk_colsum_workspace_bytes(P, K)
-                lib.dk_colsum_bf16(dy.data_ptr(), P, K, gb.data_ptr(), workspace.get(nb), nb, sst)
-            gw = grad_buffer(self, "weights", (K, C, R, S))
-            s = l2_strength(self.weight_regulariser)
-            nb = lib.dk_conv2d_wgrad_bf16_workspace_bytes(N, OH, OW, K, Cp, R, S)
-            if self._bn_in is not None:
-                lib.dk_conv2d_wgrad_bnx_bf16(dy.data_ptr(), x.data_ptr(), N, H, W, Cp, C, K, R, S, self.stride,
-                                             self.padding, OH, OW, w.data_ptr() if s else 0, s or 0.0, gw.data_ptr(),
-                                             workspace.get(nb), nb, *self._bn_in.bn_args(), sst)
-            else:
-                lib.dk_conv2d_wgrad_bf16(dy.data_ptr(), x.data_ptr(), N, H, W, Cp, C, K, R, S, self.stride,
-                                         self.padding, OH, OW, w.data_ptr() if s else 0, s or 0.0, gw.data_ptr(),
-                                         workspace.get(nb), nb, sst)
-            if s is None:
-                add_regulariser_grad(gw, w, self.weight_regulariser)
+        self._wgrad(dy)
         if not need_dx:
             return None
         Hin, Win = self.input_shape[2], self.input_shape[3]

@@ -15,11 +15,36 @@ from __future__ import annotations
 import torch
 
 from .._env import getenv
-from .._hip import HipError, deferred_wgrad_reduce, lib, stream_handle, weight_grad_stream, workspace
+from .._hip import HipError, deferred_wgrad_reduce, lib, stream_handle, workspace
 from .._tensor import BF16, empty_nhwc, ptr, to_nhwc
-from ._bn_input import BNGrad, BNOut, JoinOut, add_residual, dense_residual, lattice_operand, residual_operand
-from ._common import add_regulariser_grad, grad_buffer, init_weights, l2_strength
+from ._bn_input import NO_BN, BNGrad, BNOut, JoinOut, Partials, add_residual, bn_args, fused_residual
+from ._common import add_regulariser_grad, grad_buffer, init_weights, l2_strength, weight_grad
 from .layer import Layer
+
+# Per storage type, each entry point with the queries that size its launch (names: resolved on
+# `lib` at the call).  Forward and stride-1 dgrad: (the _ex entry, its row query).  The bf16 launches
+# run whole columns per thread: their own, smaller row counts.
+_FWD_EX = {torch.float32: ("dk_dwconv_fwd_ex_f32", "dk_dwconv_fwd_stats_rows"),
+           BF16: ("dk_dwconv_fwd_ex_bf16", "dk_dwconv_fwd_bf16_stats_rows")}
+_FWD_JOIN = ("dk_dwconv_fwd_join_f32", "dk_dwconv_fwd_stats_rows")
+_DGRAD_EX = {torch.float32: ("dk_dwconv_dgrad_ex_f32", "dk_dwconv_dgrad_stats_rows"),
+             BF16: ("dk_dwconv_dgrad_ex_bf16", "dk_dwconv_dgrad_bf16_stats_rows")}
+# The dgrad with the input's residual join (fp32); a strided _ex dgrad's row count is this query's too
+_DGRAD_JOIN = ("dk_dwconv_dgrad_join_f32", "dk_dwconv_dgrad_join_rows")
+# The one-pass backward by stride: (entry, row query, workspace query); with the input's residual
+# join (fp32 only) the same queries
+_BWD_FUSED = {1: {torch.float32: ("dk_dwconv_bwd_bnbwd_f32", "dk_dwconv_bwd_bnbwd_stats_rows",
+                                  "dk_dwconv_bwd_bnbwd_workspace_bytes"),
+                  BF16: ("dk_dwconv_bwd_bnbwd_bf16", "dk_dwconv_bwd_bnbwd_bf16_stats_rows",
+                         "dk_dwconv_bwd_bnbwd_bf16_workspace_bytes")},
+              2: {torch.float32: ("dk_dwconv_bwd_s2_bnbwd_f32", "dk_dwconv_bwd_s2_stats_rows",
+                                  "dk_dwconv_bwd_s2_workspace_bytes"),
+                  BF16: ("dk_dwconv_bwd_s2_bnbwd_bf16", "dk_dwconv_bwd_s2_stats_rows",
+                         "dk_dwconv_bwd_s2_workspace_bytes")}}
+_BWD_FUSED_JOIN = {1: ("dk_dwconv_bwd_bnbwd_join_f32", "dk_dwconv_bwd_bnbwd_stats_rows",
+                       "dk_dwconv_bwd_bnbwd_workspace_bytes"),
+                   2: ("dk_dwconv_bwd_s2_bnbwd_join_f32", "dk_dwconv_bwd_s2_stats_rows",
+                       "dk_dwconv_bwd_s2_workspace_bytes")}
 
 
 class DepthwiseConvLayer(Layer):
@@ -92,20 +117,16 @@ class DepthwiseConvLayer(Layer):
         self.num_row_patches = ((H + 2 * self.padding - R) / self.stride) + 1
         self.num_col_patches = ((W + 2 * self.padding - S) / self.stride) + 1
         OH, OW = int(self.num_row_patches), int(self.num_col_patches)
-        bf = x.dtype == BF16  # bf16 storage (BASELINE config 5): the _bf16 entry points
+        entry, rows_query = _FWD_EX[x.dtype]  # (bf16 storage, BASELINE config 5: the _bf16 entry points)
         y = empty_nhwc(N, C, OH, OW, x.dtype)
         bias = self.learned_params["bias"] if self.with_bias else None
-        stats = None
+        rows = 0
         if bn_stats is not None and not test_mode and self.stride in (1, 2):
-            rows = (lib.dk_dwconv_fwd_bf16_stats_rows if bf else lib.dk_dwconv_fwd_stats_rows)(N, OH, OW, C, self.stride)
-            if rows:
-                stats = torch.empty((rows, 2, C), dtype=torch.float64, device=x.device)
+            rows = getattr(lib, rows_query)(N, OH, OW, C, self.stride)
         w = self.learned_params["weights"]  # W[C][R][S], read in place by the _ex entry
-        fwd = lib.dk_dwconv_fwd_ex_bf16 if bf else lib.dk_dwconv_fwd_ex_f32
-        if stats is not None:
-            bn_stats.arm(stats, N * OH * OW)
-        r = fwd(x.data_ptr(), N, H, W, C, w.data_ptr(), R, S, self.stride, self.padding, ptr(bias), y.data_ptr(), OH,
-                OW, *(bn.bn_args() if bn is not None else (0, 0, 0, 0, 0)), ptr(stats), st)
+        stats = bn_stats.arm_buffer(rows, C, x.device, N * OH * OW) if rows else None
+        r = getattr(lib, entry)(x.data_ptr(), N, H, W, C, w.data_ptr(), R, S, self.stride, self.padding, ptr(bias),
+                                y.data_ptr(), OH, OW, *bn_args(bn), ptr(stats), st)
         if stats is not None:
             bn_stats.launched(stats, r)
         if not test_mode:
@@ -125,15 +146,11 @@ class DepthwiseConvLayer(Layer):
         self.num_col_patches = ((W + 2 * self.padding - S) / self.stride) + 1
         OH, OW = int(self.num_row_patches), int(self.num_col_patches)
         y = empty_nhwc(N, C, OH, OW)
-        stats = None
-        if bn_stats is not None and not test_mode:
-            rows = lib.dk_dwconv_fwd_stats_rows(N, OH, OW, C, self.stride)
-            if rows:
-                stats = torch.empty((rows, 2, C), dtype=torch.float64, device=J.device)
-        if stats is not None:
-            bn_stats.arm(stats, N * OH * OW)
-        r = lib.dk_dwconv_fwd_join_f32(*J.join_args(), N, H, W, C, self.learned_params["weights"].data_ptr(),
-                                       self.stride, 0, y.data_ptr(), OH, OW, ptr(stats), st)
+        entry, rows_query = _FWD_JOIN
+        rows = getattr(lib, rows_query)(N, OH, OW, C, self.stride) if bn_stats is not None and not test_mode else 0
+        stats = bn_stats.arm_buffer(rows, C, J.device, N * OH * OW) if rows else None
+        r = getattr(lib, entry)(*J.join_args(), N, H, W, C, self.learned_params["weights"].data_ptr(), self.stride,
+                                0, y.data_ptr(), OH, OW, ptr(stats), st)
         if stats is not None:
             bn_stats.launched(stats, r)
         J.mark_written()
@@ -195,156 +212,74 @@ class DepthwiseConvLayer(Layer):
                 or self.with_bias or not self._join_ok(join, True)):
             return False
         N, C, H, W = x.shape
-        return lib.dk_dwconv_dgrad_join_rows(N, H, W, C, self.f_rows, self.f_cols, s, self.padding) > 0
+        return getattr(lib, _DGRAD_JOIN[1])(N, H, W, C, self.f_rows, self.f_cols, s, self.padding) > 0
 
     def _backward_bn_grad(self, G, residual, need_dx, join=None):
         """One-pass backward from the following BatchNorm's deferred gradient (see
-        accepts_bn_grad): dx (+ the residual addend, + the input BatchNorm's backward partial
-        sums, or the input's residual join: see _join_ok) and the weight gradient; dy itself is
-        never written."""
+        accepts_bn_grad), stride 1 or 2: dx (+ the residual addend, + the input BatchNorm's backward
+        partial sums) and the weight gradient; dy itself is never written.  With the input's residual
+        join (fp32, _join_ok) the _join entries: dx masked by y > 0 (y = this layer's input, the
+        join's output) or by the stored mask, stage 1 of the join's BatchNorm on the store, and at
+        stride 2 a strided skip's compact lattice residual added as such."""
         st = stream_handle()
         x = self.X
         N, C, H, W = x.shape
         R, S = self.f_rows, self.f_cols
+        s2 = self.stride == 2
         w = self.learned_params["weights"]
         gw = grad_buffer(self, "weights", (C, R, S))
         s = l2_strength(self.weight_regulariser)
         bn = self._bn_in
         dx = empty_nhwc(N, C, H, W, x.dtype) if need_dx else None
-        if self.stride == 2:
-            return self._backward_bn_grad_s2(G, residual, need_dx, dx, gw, s, w, join)
-        if residual is not None:
-            residual = dense_residual(residual, (N, C, H, W))
-        res = residual_operand(residual, dx) if need_dx else None
-        if need_dx and residual is not None and res is None:
-            res = residual_operand(to_nhwc(residual), dx)
-        if join is not None and self._join_ok(join, need_dx):
-            jb = join._join_bn
-            rows = lib.dk_dwconv_bwd_bnbwd_stats_rows(N, H, W, C)
-            part = torch.empty((rows, 2, C), dtype=torch.float64, device=x.device)
-            g = to_nhwc(G.g)
-            nb = lib.dk_dwconv_bwd_bnbwd_workspace_bytes(N, H, W, C, R, S)
-            # x IS the join's output: the kernel takes the mask as x > 0 instead of reading it
-            # (DORKNET_JOIN_MASK=1 reads the stored mask)
-            from_y = getattr(join, "_join_y_ptr", None) == x.data_ptr() and getenv("DORKNET_JOIN_MASK") != "1"
-            if not from_y and join._mask is None:
-                join._mask_from_join()
-            tok = jb.arm_partials(part)
-            # the weight-gradient reduce on the side stream (not with a non-l2 regulariser, whose
-            # term is added to gw on this stream right after)
-            red = deferred_wgrad_reduce(self, nb, s is not None)
-            with red:
-                r = lib.dk_dwconv_bwd_bnbwd_join_f32(g.data_ptr(), G.x.data_ptr(), N, H, W, C, *G.bnbwd_args(),
-                                                     x.data_ptr(), w.data_ptr(), R, S, self.padding, s or 0.0,
-                                                     gw.data_ptr(), dx.data_ptr(), ptr(res),
-                                                     0 if from_y else join._mask.data_ptr(),
-                                                     jb.x.data_ptr(), jb.mean.data_ptr(), jb.invstd.data_ptr(),
-                                                     part.data_ptr(), red.ws, nb, st)
-            red.flush()
-            if s is None:
-                add_regulariser_grad(gw, w, self.weight_regulariser)
-            jb.hand_backward_partials(dx, part, r, tok)
+        joined = join is not None and not (s2 and x.dtype == BF16) and self._join_ok(join, need_dx)
+        residual, res, lat = fused_residual(residual, dx, 2 if joined and s2 else 0) if need_dx else (None, None, 0)
+        if s2 and not joined and residual is not None and res is None:
+            raise NotImplementedError("{}: the fused stride-2 backward needs an NHWC residual".format(self.layer_name))
+        entry, rows_query, ws_query = _BWD_FUSED_JOIN[self.stride] if joined else _BWD_FUSED[self.stride][x.dtype]
+        # the BatchNorm whose stage 1 rides on the dx store: the join's, or this layer's input's
+        pbn = join._join_bn if joined else bn if need_dx else None
+        rows = getattr(lib, rows_query)(N, H, W, C) if pbn is not None else 0
+        g = to_nhwc(G.g)
+        if s2:
+            geometry, filt = (N, H, W, C, (H + 1) // 2, (W + 1) // 2), ()
+            nb = getattr(lib, ws_query)(N, H, W, C)
+        else:
+            geometry, filt = (N, H, W, C), (R, S, self.padding)
+            nb = getattr(lib, ws_query)(N, H, W, C, R, S)
+        if not joined:
+            on_load = bn_args(bn)
+        else:
+            if s2:
+                mask = lat  # (the mask is y > 0; this operand says how the residual is laid out)
+            else:
+                # x IS the join's output: the kernel takes the mask as x > 0 instead of reading it
+                # (DORKNET_JOIN_MASK=1 reads the stored mask)
+                from_y = getattr(join, "_join_y_ptr", None) == x.data_ptr() and getenv("DORKNET_JOIN_MASK") != "1"
+                if not from_y and join._mask is None:
+                    join._mask_from_join()
+                mask = 0 if from_y else join._mask.data_ptr()
+            on_load = (mask, pbn.x.data_ptr(), pbn.mean.data_ptr(), pbn.invstd.data_ptr())
+        part = Partials(pbn, rows, C, x.device)
+        # the weight-gradient reduce on the side stream (not with a non-l2 regulariser, whose term
+        # is added to gw on this stream right after)
+        red = deferred_wgrad_reduce(self, nb, s is not None)
+        with red:
+            r = getattr(lib, entry)(g.data_ptr(), G.x.data_ptr(), *geometry, *G.bnbwd_args(), x.data_ptr(),
+                                    w.data_ptr(), *filt, s or 0.0, gw.data_ptr(), ptr(dx), ptr(res), *on_load,
+                                    part.ptr, red.ws, nb, st)
+        red.flush()
+        if s is None:
+            add_regulariser_grad(gw, w, self.weight_regulariser)
+        if not need_dx:
+            return None
+        part.hand(dx, r)
+        if joined:
             join.join_backward_done()
-            if residual is not None and res is None:
+            if not s2 and residual is not None and res is None:
                 raise RuntimeError("{}: the fused join needs the residual in the dgrad epilogue".format(
                     self.layer_name))
-            return dx
-        part = None
-        bf = x.dtype == BF16
-        if need_dx and bn is not None:
-            rows = (lib.dk_dwconv_bwd_bnbwd_bf16_stats_rows if bf else lib.dk_dwconv_bwd_bnbwd_stats_rows)(N, H, W, C)
-            part = torch.empty((rows, 2, C), dtype=torch.float64, device=x.device)
-        g = to_nhwc(G.g)
-        nb = (lib.dk_dwconv_bwd_bnbwd_bf16_workspace_bytes if bf else lib.dk_dwconv_bwd_bnbwd_workspace_bytes)(
-            N, H, W, C, R, S)
-        tok = bn.arm_partials(part) if part is not None else None
-        red = deferred_wgrad_reduce(self, nb, s is not None)
-        with red:
-            r = (lib.dk_dwconv_bwd_bnbwd_bf16 if bf else lib.dk_dwconv_bwd_bnbwd_f32)(
-                g.data_ptr(), G.x.data_ptr(), N, H, W, C, *G.bnbwd_args(), x.data_ptr(), w.data_ptr(), R, S,
-                self.padding, s or 0.0, gw.data_ptr(), ptr(dx), ptr(res),
-                *(bn.bn_args() if bn is not None else (0, 0, 0, 0, 0)), ptr(part), red.ws, nb, st)
-        red.flush()
-        if s is None:
-            add_regulariser_grad(gw, w, self.weight_regulariser)
-        if not need_dx:
-            return None
-        if part is not None:
-            bn.hand_backward_partials(dx, part, r, tok)
-        if residual is not None and res is None:
+        elif residual is not None and res is None:
             dx = add_residual(dx, residual)  # (a new tensor: the BN then recomputes its sums)
-        return dx
-
-    def _backward_bn_grad_s2(self, G, residual, need_dx, dx, gw, s, w, join=None):
-        """The stride-2 form of _backward_bn_grad (dk_dwconv_bwd_s2_bnbwd_*): dx (+ the residual,
-        + the input BatchNorm's backward partial sums) and the weight gradient, dy never written.
-        With the input's residual join (fp32, _join_ok): dk_dwconv_bwd_s2_bnbwd_join_f32 -- dx
-        masked by y > 0 (y = this layer's input, the join's output), stage 1 of the join's
-        BatchNorm on the store, a strided skip's compact lattice residual added as such."""
-        st = stream_handle()
-        x = self.X
-        N, C, H, W = x.shape
-        OH, OW = (H + 1) // 2, (W + 1) // 2
-        bn = self._bn_in
-        bf = x.dtype == BF16
-        if join is not None and need_dx and not bf and self._join_ok(join, True):
-            return self._backward_bn_grad_s2_join(G, residual, dx, gw, s, w, join)
-        if residual is not None:
-            residual = dense_residual(residual, (N, C, H, W))
-        res = residual_operand(residual, dx) if need_dx else None
-        if need_dx and residual is not None and res is None:
-            res = residual_operand(to_nhwc(residual), dx)
-        if need_dx and residual is not None and res is None:
-            raise NotImplementedError("{}: the fused stride-2 backward needs an NHWC residual".format(self.layer_name))
-        part = None
-        if need_dx and bn is not None:
-            part = torch.empty((lib.dk_dwconv_bwd_s2_stats_rows(N, H, W, C), 2, C), dtype=torch.float64,
-                               device=x.device)
-        g = to_nhwc(G.g)
-        nb = lib.dk_dwconv_bwd_s2_workspace_bytes(N, H, W, C)
-        tok = bn.arm_partials(part) if part is not None else None
-        red = deferred_wgrad_reduce(self, nb, s is not None)
-        with red:
-            r = (lib.dk_dwconv_bwd_s2_bnbwd_bf16 if bf else lib.dk_dwconv_bwd_s2_bnbwd_f32)(
-                g.data_ptr(), G.x.data_ptr(), N, H, W, C, OH, OW, *G.bnbwd_args(), x.data_ptr(), w.data_ptr(),
-                s or 0.0, gw.data_ptr(), ptr(dx), ptr(res),
-                *(bn.bn_args() if bn is not None else (0, 0, 0, 0, 0)), ptr(part), red.ws, nb, st)
-        red.flush()
-        if s is None:
-            add_regulariser_grad(gw, w, self.weight_regulariser)
-        if not need_dx:
-            return None
-        if part is not None:
-            bn.hand_backward_partials(dx, part, r, tok)
-        return dx
-
-    def _backward_bn_grad_s2_join(self, G, residual, dx, gw, s, w, join):
-        st = stream_handle()
-        x = self.X
-        N, C, H, W = x.shape
-        OH, OW = (H + 1) // 2, (W + 1) // 2
-        jb = join._join_bn
-        lat = lattice_operand(residual, dx, 2)
-        if lat is None and residual is not None:
-            residual = dense_residual(residual, (N, C, H, W))
-        res = lat if lat is not None else residual_operand(residual, dx)
-        if residual is not None and res is None:
-            res = residual_operand(to_nhwc(residual), dx)
-        part = torch.empty((lib.dk_dwconv_bwd_s2_stats_rows(N, H, W, C), 2, C), dtype=torch.float64, device=x.device)
-        g = to_nhwc(G.g)
-        nb = lib.dk_dwconv_bwd_s2_workspace_bytes(N, H, W, C)
-        tok = jb.arm_partials(part)
-        red = deferred_wgrad_reduce(self, nb, s is not None)
-        with red:
-            r = lib.dk_dwconv_bwd_s2_bnbwd_join_f32(
-                g.data_ptr(), G.x.data_ptr(), N, H, W, C, OH, OW, *G.bnbwd_args(), x.data_ptr(), w.data_ptr(),
-                s or 0.0, gw.data_ptr(), dx.data_ptr(), ptr(res), 2 if lat is not None else 0, jb.x.data_ptr(),
-                jb.mean.data_ptr(), jb.invstd.data_ptr(), part.data_ptr(), red.ws, nb, st)
-        red.flush()
-        if s is None:
-            add_regulariser_grad(gw, w, self.weight_regulariser)
-        jb.hand_backward_partials(dx, part, r, tok)
-        join.join_backward_done()
         return dx
 
     def backward(self, upstream_dx, residual=None, need_dx=True, join=None):
@@ -359,49 +294,34 @@ class DepthwiseConvLayer(Layer):
         N, C, H, W = x.shape
         R, S = self.f_rows, self.f_cols
         OH, OW = int(self.num_row_patches), int(self.num_col_patches)
-        P = N * OH * OW
         w = self.learned_params["weights"]
         bf = x.dtype == BF16
         if bf and (dy.dtype != BF16 or self.with_bias):
             raise NotImplementedError("{}: bf16 storage needs a bf16 gradient and no bias".format(self.layer_name))
-        # the weight gradient runs on the side stream (_hip.weight_grad_stream)
-        with weight_grad_stream(dy, x, *self._bn_tensors()):
-            sst = stream_handle()
-            if self.with_bias:
-                gb = grad_buffer(self, "bias", (C,))
-                nb = lib.dk_colsum_workspace_bytes(P, C)
-                lib.dk_colsum_f32(dy.data_ptr(), P, C, gb.data_ptr(), workspace.get(nb), nb, sst)
-            gw = grad_buffer(self, "weights", (C, R, S))
-            s = l2_strength(self.weight_regulariser)
-            nb = lib.dk_dwconv_wgrad_workspace_bytes(N, OH, OW, C, R, S)
+        bn = self._bn_in
+        wnb = lib.dk_dwconv_wgrad_workspace_bytes(N, OH, OW, C, R, S)
+
+        def launch(wl2, s, gw, sst):
+            args = (dy.data_ptr(), x.data_ptr(), N, H, W, C, R, S, self.stride, self.padding, OH, OW, wl2, s, gw,
+                    workspace.get(wnb), wnb)
             if bf:
-                lib.dk_dwconv_wgrad_bnx_bf16(
-                    dy.data_ptr(), x.data_ptr(), N, H, W, C, R, S, self.stride, self.padding, OH, OW,
-                    w.data_ptr() if s else 0, s or 0.0, gw.data_ptr(), workspace.get(nb), nb,
-                    *(self._bn_in.bn_args() if self._bn_in is not None else (0, 0, 0, 0, 0)), sst)
-            elif self._bn_in is not None:
-                lib.dk_dwconv_wgrad_bnx_f32(dy.data_ptr(), x.data_ptr(), N, H, W, C, R, S, self.stride,
-                                            self.padding, OH, OW, w.data_ptr() if s else 0, s or 0.0, gw.data_ptr(),
-                                            workspace.get(nb), nb, *self._bn_in.bn_args(), sst)
+                lib.dk_dwconv_wgrad_bnx_bf16(*args, *bn_args(bn), sst)
+            elif bn is not None:
+                lib.dk_dwconv_wgrad_bnx_f32(*args, *bn.bn_args(), sst)
             else:
-                lib.dk_dwconv_wgrad_f32(dy.data_ptr(), x.data_ptr(), N, H, W, C, R, S, self.stride, self.padding, OH,
-                                        OW, w.data_ptr() if s else 0, s or 0.0, gw.data_ptr(), workspace.get(nb), nb,
-                                        sst)
-            if s is None:
-                add_regulariser_grad(gw, w, self.weight_regulariser)
+                lib.dk_dwconv_wgrad_f32(*args, sst)
+        weight_grad(self, dy, x, N * OH * OW, C, (C, R, S), launch)
         if not need_dx:
             return None
         dx = empty_nhwc(N, C, H, W, x.dtype)
         nb = lib.dk_dwconv_dgrad_workspace_bytes(C, R, S)
-        dgrad_ex = lib.dk_dwconv_dgrad_ex_bf16 if bf else lib.dk_dwconv_dgrad_ex_f32
-        bn = self._bn_in
-        jrows = (lib.dk_dwconv_dgrad_join_rows(N, H, W, C, R, S, self.stride, self.padding)
+        entry, rows_query = _DGRAD_EX[x.dtype]
+        join_entry, join_rows_query = _DGRAD_JOIN
+        geometry = (dy.data_ptr(), N, OH, OW, C, w.data_ptr(), R, S, self.stride, self.padding, dx.data_ptr(), H, W)
+        jrows = (getattr(lib, join_rows_query)(N, H, W, C, R, S, self.stride, self.padding)
                  if join is not None and not bf and self._join_ok(join, True) else 0)
         # a residual handed over as its compact lattice is added as such by the join dgrad only
-        lat = lattice_operand(residual, dx, self.stride) if jrows else None
-        if lat is None and residual is not None:
-            residual = dense_residual(residual, (N, C, H, W))
-        res = lat if lat is not None else residual_operand(residual, dx)
+        residual, res, lat = fused_residual(residual, dx, self.stride if jrows else 0, retry=False)
         if residual is not None and res is None:
             jrows = 0
         # the input BatchNorm's stage-1 partials ride on the dgrad store: stride 1 in the dgrad's
@@ -409,48 +329,39 @@ class DepthwiseConvLayer(Layer):
         rows = 0
         if bn is not None and R == S:
             if self.stride == 1:
-                # (the bf16 launch runs whole columns per thread: its own, smaller row count)
-                rows = (lib.dk_dwconv_dgrad_bf16_stats_rows if bf else lib.dk_dwconv_dgrad_stats_rows)(N, H, W, C, 1)
+                rows = getattr(lib, rows_query)(N, H, W, C, 1)
             else:
-                rows = lib.dk_dwconv_dgrad_join_rows(N, H, W, C, R, S, self.stride, self.padding)
+                rows = getattr(lib, join_rows_query)(N, H, W, C, R, S, self.stride, self.padding)
         if rows and self.padding <= R - 1 and (residual is None or res is not None):
             # + stage 1 of the input BatchNorm's backward, in the dgrad epilogue (+ the residual)
-            part = torch.empty((rows, 2, C), dtype=torch.float64, device=dx.device)
-            tok = bn.arm_partials(part)
-            r = dgrad_ex(dy.data_ptr(), N, OH, OW, C, w.data_ptr(), R, S, self.stride, self.padding, dx.data_ptr(), H,
-                         W, workspace.get(nb), nb, ptr(res), bn.x.data_ptr(), *bn.bn_args(), part.data_ptr(), st)
-            bn.hand_backward_partials(dx, part, r, tok)
+            part = Partials(bn, rows, C, dx.device)
+            r = getattr(lib, entry)(*geometry, workspace.get(nb), nb, ptr(res), bn.x.data_ptr(), *bn.bn_args(),
+                                    part.ptr, st)
+            part.hand(dx, r)
             return dx
         if jrows:
             # the input's residual join: its ReLU backward and its BatchNorm's stage 1 on the store
             jb = join._join_bn
             if join._mask is None:
                 join._mask_from_join()
-            part = torch.empty((jrows, 2, C), dtype=torch.float64, device=dx.device)
-            tok = jb.arm_partials(part)
-            r = lib.dk_dwconv_dgrad_join_f32(dy.data_ptr(), N, OH, OW, C, w.data_ptr(), R, S, self.stride,
-                                             self.padding, dx.data_ptr(), H, W, workspace.get(nb), nb, ptr(res),
-                                             self.stride if lat is not None else 0, join._mask.data_ptr(), jb.x.data_ptr(), jb.mean.data_ptr(),
-                                             jb.invstd.data_ptr(), part.data_ptr(), st)
-            jb.hand_backward_partials(dx, part, r, tok)
+            part = Partials(jb, jrows, C, dx.device)
+            r = getattr(lib, join_entry)(*geometry, workspace.get(nb), nb, ptr(res), lat, join._mask.data_ptr(),
+                                         jb.x.data_ptr(), jb.mean.data_ptr(), jb.invstd.data_ptr(), part.ptr, st)
+            part.hand(dx, r)
             join.join_backward_done()
             return dx
         if bf:
             if residual is not None and res is None:
                 raise NotImplementedError("{}: bf16 residual must be a bf16 NHWC tensor".format(self.layer_name))
-            dgrad_ex(dy.data_ptr(), N, OH, OW, C, w.data_ptr(), R, S, self.stride, self.padding, dx.data_ptr(), H, W,
-                     workspace.get(nb), nb, ptr(res), 0, 0, 0, 0, 0, 0, 0, st)
+            getattr(lib, entry)(*geometry, workspace.get(nb), nb, ptr(res), 0, *NO_BN, 0, st)
             return dx
         if res is not None:
             try:
-                lib.dk_dwconv_dgrad_ex_f32(dy.data_ptr(), N, OH, OW, C, w.data_ptr(), R, S, self.stride,
-                                           self.padding, dx.data_ptr(), H, W, workspace.get(nb), nb, res.data_ptr(),
-                                           0, 0, 0, 0, 0, 0, 0, st)
+                getattr(lib, entry)(*geometry, workspace.get(nb), nb, res.data_ptr(), 0, *NO_BN, 0, st)
                 return dx
             except HipError:  # geometry without a fused residual (generic gather dgrad)
                 pass
-        lib.dk_dwconv_dgrad_f32(dy.data_ptr(), N, OH, OW, C, w.data_ptr(), R, S, self.stride, self.padding,
-                                dx.data_ptr(), H, W, workspace.get(nb), nb, st)
+        lib.dk_dwconv_dgrad_f32(*geometry, workspace.get(nb), nb, st)
         return add_residual(dx, residual) if residual is not None else dx
 
     def save_to_h5(self, open_f, save_grads=True):

@@ -24,9 +24,34 @@ import torch
 from .._env import getenv
 from .._hip import deferred_wgrad_reduce, lib, stream_handle, weight_grad_stream, workspace
 from .._tensor import BF16, empty_nhwc, ptr, to_nhwc
-from ._bn_input import BNGrad, BNOut, add_residual, residual_operand
-from ._common import add_regulariser_grad, grad_buffer, init_weights, l2_strength
+from ._bn_input import BNGrad, BNOut, Partials, add_residual, bn_args, residual_operand
+from ._common import add_regulariser_grad, grad_buffer, init_weights, l2_strength, weight_grad
 from .layer import Layer
+
+# Per storage type, each entry point with the queries that size its launch (names: resolved on
+# `lib` at the call; a named query is called as (N, OH, OW, K, C)).
+# Forward and dgrad: (the _ex entry, its row query).  The fp32 and bf16 queries take different
+# arguments (bf16: a strided launch never takes the streaming kernels, so the stride counts).
+_FWD_EX = {torch.float32: ("dk_pwconv_fwd_ex_f32",
+                           lambda N, OH, OW, K, C, s: lib.dk_pwconv_fwd_stats_rows(N, OH, OW, K, C)),
+           BF16: ("dk_pwconv_fwd_ex_bf16",
+                  lambda N, OH, OW, K, C, s: lib.dk_pwconv_fwd_bf16_strided_stats_rows(N, OH, OW, K, C, s))}
+_DGRAD_EX = {torch.float32: ("dk_pwconv_dgrad_ex_f32",
+                             lambda N, OH, OW, K, C, s: lib.dk_pwconv_dgrad_stats_rows(N, OH, OW, K, C)),
+             BF16: ("dk_pwconv_dgrad_ex_bf16",
+                    lambda N, OH, OW, K, C, s: lib.dk_pwconv_dgrad_bf16_stats_rows(N, OH, OW, K, C, s))}
+# The dgrad into the compact lattice (fp32), and the dgrad that applies the following BatchNorm's
+# backward on load: (entry, row query)
+_DGRAD_LATTICE = ("dk_pwconv_dgrad_lattice_f32", "dk_pwconv_dgrad_stats_rows")
+_DGRAD_BNBWD = {torch.float32: ("dk_pwconv_dgrad_bnbwd_f32", "dk_pwconv_dgrad_bnbwd_stats_rows"),
+                BF16: ("dk_pwconv_dgrad_bnbwd_bf16", "dk_pwconv_dgrad_bnbwd_bf16_stats_rows")}
+# The one-pass backward: (entry, row query, workspace query); its lattice form is fp32 only
+_BWD_FUSED = {torch.float32: ("dk_pwconv_bwd_bnbwd_f32", "dk_pwconv_bwd_fused_rows",
+                              "dk_pwconv_bwd_fused_workspace_bytes"),
+              BF16: ("dk_pwconv_bwd_bnbwd_bf16", "dk_pwconv_bwd_fused_bf16_rows",
+                     "dk_pwconv_bwd_fused_bf16_workspace_bytes")}
+_BWD_FUSED_LATTICE = ("dk_pwconv_bwd_bnbwd_lattice_f32", "dk_pwconv_bwd_fused_rows",
+                      "dk_pwconv_bwd_fused_workspace_bytes")
 
 
 class PointwiseConvLayer(Layer):
@@ -95,19 +120,14 @@ class PointwiseConvLayer(Layer):
             w = self._padded_weights(w, Cp)
         self._wp = w
         bias = self.learned_params["bias"] if self.with_bias else None
-        stats = None
-        if bn_stats is not None and not test_mode:
-            # (bf16: a strided launch never takes the streaming kernels, so the query takes the stride)
-            rows = (lib.dk_pwconv_fwd_bf16_strided_stats_rows(N, OH, OW, K, Cp, s) if bf
-                    else lib.dk_pwconv_fwd_stats_rows(N, OH, OW, K, Cp))
-            stats = torch.empty((rows, 2, K), dtype=torch.float64, device=x.device)
-        if bn is not None or stats is not None or bf:
-            fwd = lib.dk_pwconv_fwd_ex_bf16 if bf else lib.dk_pwconv_fwd_ex_f32
-            if stats is not None:
-                bn_stats.arm(stats, N * OH * OW)
-            r = fwd(x.data_ptr(), N, H, W, Cp, w.data_ptr(), K, s, ptr(bias), y.data_ptr(), OH, OW,
-                    *(bn.bn_args() if bn is not None else (0, 0, 0, 0, 0)), ptr(stats), st)
-            if stats is not None:
+        want_stats = bn_stats is not None and not test_mode
+        if bn is not None or want_stats or bf:
+            entry, rows_query = _FWD_EX[x.dtype]
+            stats = (bn_stats.arm_buffer(rows_query(N, OH, OW, K, Cp, s), K, x.device, N * OH * OW)
+                     if want_stats else None)
+            r = getattr(lib, entry)(x.data_ptr(), N, H, W, Cp, w.data_ptr(), K, s, ptr(bias), y.data_ptr(), OH, OW,
+                                    *bn_args(bn), ptr(stats), st)
+            if want_stats:
                 bn_stats.launched(stats, r)
         else:
             lib.dk_pwconv_fwd_f32(x.data_ptr(), N, H, W, Cp, w.data_ptr(), K, s, ptr(bias), y.data_ptr(), OH, OW, st)
@@ -143,7 +163,7 @@ class PointwiseConvLayer(Layer):
         N = x.shape[0]
         OH, OW = self.out_hw
         return (tuple(bx.shape) == (N, self.num_filters, OH, OW)
-                and lib.dk_pwconv_bwd_fused_rows(N, OH, OW, self.num_filters, self.num_channels) > 0
+                and getattr(lib, _BWD_FUSED_LATTICE[1])(N, OH, OW, self.num_filters, self.num_channels) > 0
                 and self.num_filters == 64 and self.num_channels == 64)
 
     def _takes_bn_grad(self, bx):
@@ -178,21 +198,18 @@ class PointwiseConvLayer(Layer):
         N, C, H, W = x.shape
         K, s = self.num_filters, self.stride
         OH, OW = self.out_hw
-        P = N * OH * OW
-        w = self.learned_params["weights"]
         if isinstance(upstream_dx, BNGrad):
             if need_dx and lattice_out and self._lattice_fused_ok(upstream_dx.x, residual):
-                return self._bwd_fused_lattice(upstream_dx, st)
+                return self._bwd_fused(upstream_dx, None, st, lattice=True)
             if need_dx and self._fused_bwd_ok(upstream_dx, residual):
                 # input gradient, weight gradient and the input BN's partials in one pass; dy
                 # is formed from the BatchNorm's gradient as it is loaded and never stored
                 return self._bwd_fused(upstream_dx, residual, st)
             if need_dx and self._takes_bn_grad(upstream_dx.x):
                 # dgrad first: it forms (and stores) dy from the BatchNorm's gradient as it loads it
-                bf = x.dtype == BF16
                 dy = empty_nhwc(N, K, OH, OW, x.dtype)
-                dx = (self._dgrad_bnbwd_bf16 if bf else self._dgrad_bnbwd)(upstream_dx, dy, residual, st)
-                self._wgrad(dy, x, N, H, W, C, K, s, OH, OW, P, w, bf)
+                dx = self._dgrad_bnbwd(upstream_dx, dy, residual, st)
+                self._wgrad(dy)
                 return dx
             upstream_dx = upstream_dx.materialize()
         dy = to_nhwc(upstream_dx)
@@ -201,7 +218,7 @@ class PointwiseConvLayer(Layer):
             return self._backward_padded(dy, residual, need_dx, st)
         if bf and dy.dtype != BF16:
             raise NotImplementedError("{}: bf16 storage needs a bf16 gradient".format(self.layer_name))
-        self._wgrad(dy, x, N, H, W, C, K, s, OH, OW, P, w, bf)
+        self._wgrad(dy)
         if need_dx and lattice_out and residual is None and not bf and self.lattice_ok():
             return self._dgrad_lattice(dy, st)
         return self._dgrad(dy, residual, st) if need_dx else None
@@ -221,13 +238,12 @@ class PointwiseConvLayer(Layer):
                                     dx.data_ptr(), st)
             dx._dk_lattice = s
             return dx
-        rows = lib.dk_pwconv_dgrad_stats_rows(N, OH, OW, K, C)
-        part = torch.empty((rows, 2, C), dtype=torch.float64, device=dx.device)
-        tok = bn.arm_partials(part)
-        r = lib.dk_pwconv_dgrad_lattice_f32(dy.data_ptr(), N, OH, OW, K, self.learned_params["weights"].data_ptr(), C,
-                                            s, dx.data_ptr(), bn.x.data_ptr(), *bn.bn_args(), part.data_ptr(), st)
+        entry, rows_query = _DGRAD_LATTICE
+        part = Partials(bn, getattr(lib, rows_query)(N, OH, OW, K, C), C, dx.device)
+        r = getattr(lib, entry)(dy.data_ptr(), N, OH, OW, K, self.learned_params["weights"].data_ptr(), C, s,
+                                dx.data_ptr(), bn.x.data_ptr(), *bn.bn_args(), part.ptr, st)
         dx._dk_lattice = s
-        bn.hand_backward_partials(dx, part, r, tok)
+        part.hand(dx, r)
         return dx
 
     def _backward_padded(self, dy, residual, need_dx, st):
@@ -236,23 +252,11 @@ class PointwiseConvLayer(Layer):
         N, Cp, H, W = x.shape
         C, K, s = self.num_channels, self.num_filters, self.stride
         OH, OW = self.out_hw
-        P = N * OH * OW
-        w = self.learned_params["weights"]
-        with weight_grad_stream(dy, x):
-            sst = stream_handle()
-            if self.with_bias:
-                gb = grad_buffer(self, "bias", (K,))
-                nb = lib.dk_colsum_workspace_bytes(P, K)
-                lib.dk_colsum_f32(dy.data_ptr(), P, K, gb.data_ptr(), workspace.get(nb), nb, sst)
-            gw = grad_buffer(self, "weights", (K, C))
-            l2s = l2_strength(self.weight_regulariser)
-            # the conv weight gradient with R = S = 1, pad 0: its reduce scatters (K, Cp) -> (K, C)
-            nb = lib.dk_conv2d_wgrad_workspace_bytes(N, OH, OW, K, Cp, 1, 1)
-            lib.dk_conv2d_wgrad_f32(dy.data_ptr(), x.data_ptr(), N, H, W, Cp, C, K, 1, 1, s, 0, OH, OW,
-                                    w.data_ptr() if l2s else 0, l2s or 0.0, gw.data_ptr(), workspace.get(nb), nb,
-                                    sst)
-            if l2s is None:
-                add_regulariser_grad(gw, w, self.weight_regulariser)
+        # the conv weight gradient with R = S = 1, pad 0: its reduce scatters (K, Cp) -> (K, C)
+        nb = lib.dk_conv2d_wgrad_workspace_bytes(N, OH, OW, K, Cp, 1, 1)
+        weight_grad(self, dy, x, N * OH * OW, K, (K, C), lambda wl2, l2s, gw, sst: lib.dk_conv2d_wgrad_f32(
+            dy.data_ptr(), x.data_ptr(), N, H, W, Cp, C, K, 1, 1, s, 0, OH, OW, wl2, l2s, gw, workspace.get(nb), nb,
+            sst))
         if not need_dx:
             return None
         dxp = empty_nhwc(N, Cp, OH * s, OW * s)
@@ -275,14 +279,10 @@ class PointwiseConvLayer(Layer):
             return False
         N, C, H, W = x.shape
         OH, OW = self.out_hw
-        if x.dtype == BF16:
-            if lib.dk_pwconv_bwd_fused_bf16_rows(N, OH, OW, self.num_filters, C) <= 0:
-                return False
-        elif x.dtype != torch.float32:
+        row = _BWD_FUSED.get(x.dtype)
+        if row is None or getattr(lib, row[1])(N, OH, OW, self.num_filters, C) <= 0:
             return False
-        else:
-            if lib.dk_pwconv_bwd_fused_rows(N, OH, OW, self.num_filters, C) <= 0:
-                return False
+        if x.dtype == torch.float32:
             env = getenv("DORKNET_PW_FUSED_BWD")
             if env is not None:
                 if env != "1":
@@ -293,35 +293,31 @@ class PointwiseConvLayer(Layer):
             return False
         return True
 
-    def _bwd_fused(self, bg, residual, st):
+    def _bwd_fused(self, bg, residual, st, lattice=False):
+        """The one-pass backward (_fused_bwd_ok); `lattice`: its strided form, whose dx is the compact
+        stride-s lattice (_lattice_fused_ok: fp32, the input a BNOut, no residual)."""
         x = self.X
         N, C, H, W = x.shape
-        K = self.num_filters
+        K, s = self.num_filters, self.stride
         OH, OW = self.out_hw
         w = self.learned_params["weights"]
-        bf = x.dtype == BF16
+        entry, rows_query, ws_query = _BWD_FUSED_LATTICE if lattice else _BWD_FUSED[x.dtype]
         dx = empty_nhwc(N, C, OH, OW, x.dtype)
         bn = self._bn_in
-        res = residual_operand(residual, dx)
+        operands = (x.data_ptr(), H, W, s) if lattice else (ptr(residual_operand(residual, dx)), x.data_ptr())
         g = to_nhwc(bg.g)
-        part = None
-        rows_fn = lib.dk_pwconv_bwd_fused_bf16_rows if bf else lib.dk_pwconv_bwd_fused_rows
-        if bn is not None:
-            rows = rows_fn(N, OH, OW, K, C)
-            part = torch.empty((rows, 2, C), dtype=torch.float64, device=dx.device)
+        rows = getattr(lib, rows_query)(N, OH, OW, K, C) if bn is not None else 0
         gw = grad_buffer(self, "weights", (K, C))
         l2s = l2_strength(self.weight_regulariser)
-        nb = (lib.dk_pwconv_bwd_fused_bf16_workspace_bytes if bf else lib.dk_pwconv_bwd_fused_workspace_bytes)(
-            N, OH, OW, K, C)
-        tok = bn.arm_partials(part) if bn is not None else None
+        nb = getattr(lib, ws_query)(N, OH, OW, K, C)
+        part = Partials(bn, rows, C, dx.device)
         # the weight-gradient reduce on the side stream (not with a non-l2 regulariser, whose term
         # is added to gw on this stream right after)
         red = deferred_wgrad_reduce(self, nb, l2s is not None)
         with red:
-            r = (lib.dk_pwconv_bwd_bnbwd_bf16 if bf else lib.dk_pwconv_bwd_bnbwd_f32)(
-                g.data_ptr(), bg.x.data_ptr(), N, OH, OW, K, *bg.bnbwd_args(), w.data_ptr(), C, l2s or 0.0,
-                gw.data_ptr(), dx.data_ptr(), ptr(res), x.data_ptr(),
-                *((*bn.bn_args(), part.data_ptr()) if bn is not None else (0,) * 6), red.ws, nb, st)
+            r = getattr(lib, entry)(g.data_ptr(), bg.x.data_ptr(), N, OH, OW, K, *bg.bnbwd_args(), w.data_ptr(), C,
+                                    l2s or 0.0, gw.data_ptr(), dx.data_ptr(), *operands, *bn_args(bn), part.ptr,
+                                    red.ws, nb, st)
         red.flush()
         if l2s is None:
             add_regulariser_grad(gw, w, self.weight_regulariser)
@@ -330,117 +326,53 @@ class PointwiseConvLayer(Layer):
             # here on (a data-parallel bucket's all-reduce) must follow it
             with weight_grad_stream():
                 pass
-        if bn is not None:
-            bn.hand_backward_partials(dx, part, r, tok)
-        return dx
-
-    def _bwd_fused_lattice(self, bg, st):
-        x = self.X
-        N, C, H, W = x.shape
-        K, s = self.num_filters, self.stride
-        OH, OW = self.out_hw
-        w = self.learned_params["weights"]
-        dx = empty_nhwc(N, C, OH, OW)
-        bn = self._bn_in
-        rows = lib.dk_pwconv_bwd_fused_rows(N, OH, OW, K, C)
-        part = torch.empty((rows, 2, C), dtype=torch.float64, device=dx.device)
-        gw = grad_buffer(self, "weights", (K, C))
-        l2s = l2_strength(self.weight_regulariser)
-        nb = lib.dk_pwconv_bwd_fused_workspace_bytes(N, OH, OW, K, C)
-        tok = bn.arm_partials(part)
-        red = deferred_wgrad_reduce(self, nb, l2s is not None)
-        with red:
-            r = lib.dk_pwconv_bwd_bnbwd_lattice_f32(
-                to_nhwc(bg.g).data_ptr(), bg.x.data_ptr(), N, OH, OW, K, *bg.bnbwd_args(), w.data_ptr(), C,
-                l2s or 0.0, gw.data_ptr(), dx.data_ptr(), x.data_ptr(), H, W, s, *bn.bn_args(), part.data_ptr(),
-                red.ws, nb, st)
-        red.flush()
-        if l2s is None:
-            add_regulariser_grad(gw, w, self.weight_regulariser)
-        if not red.on:
-            with weight_grad_stream():
-                pass
-        dx._dk_lattice = s
-        bn.hand_backward_partials(dx, part, r, tok)
+        if lattice:
+            dx._dk_lattice = s
+        part.hand(dx, r)
         return dx
 
     def _dgrad_bnbwd(self, bg, dy_out, residual, st):
+        """The dgrad that forms dy from the following BatchNorm's gradient as it loads it and stores
+        it to dy_out for the weight gradient (bf16 storage: rounded to bf16 for the MFMA and for
+        dy_out); the input BatchNorm's partials over the stored dx."""
         x = self.X
         N, C, H, W = x.shape
         K = self.num_filters
         OH, OW = self.out_hw
         w = self.learned_params["weights"]
-        dx = empty_nhwc(N, C, OH, OW)
+        entry, rows_query = _DGRAD_BNBWD[x.dtype]
+        dx = empty_nhwc(N, C, OH, OW, x.dtype)
         bn = self._bn_in
         res = residual_operand(residual, dx)
+        if x.dtype == BF16 and residual is not None and res is None:
+            raise NotImplementedError("{}: bf16 residual must be a bf16 NHWC tensor".format(self.layer_name))
         g = to_nhwc(bg.g)
-        part = None
-        if bn is not None:
-            rows = lib.dk_pwconv_dgrad_bnbwd_stats_rows(N, OH, OW, K, C)
-            part = torch.empty((rows, 2, C), dtype=torch.float64, device=dx.device)
-        tok = bn.arm_partials(part) if bn is not None else None
-        r = lib.dk_pwconv_dgrad_bnbwd_f32(g.data_ptr(), bg.x.data_ptr(), N, OH, OW, K, *bg.bnbwd_args(),
-                                          dy_out.data_ptr(), w.data_ptr(), C, dx.data_ptr(), ptr(res),
-                                          *((bn.x.data_ptr(), *bn.bn_args(), part.data_ptr()) if bn is not None
-                                            else (0, 0, 0, 0, 0, 0, 0)), st)
-        if bn is not None:
-            bn.hand_backward_partials(dx, part, r, tok)
+        part = Partials(bn, getattr(lib, rows_query)(N, OH, OW, K, C) if bn is not None else 0, C, dx.device)
+        r = getattr(lib, entry)(g.data_ptr(), bg.x.data_ptr(), N, OH, OW, K, *bg.bnbwd_args(), dy_out.data_ptr(),
+                                w.data_ptr(), C, dx.data_ptr(), ptr(res), bn.x.data_ptr() if bn is not None else 0,
+                                *bn_args(bn), part.ptr, st)
+        part.hand(dx, r)
         if residual is not None and res is None:
             dx = add_residual(dx, residual)
         return dx
 
-    def _dgrad_bnbwd_bf16(self, bg, dy_out, residual, st):
-        """bf16 storage: dk_pwconv_dgrad_bnbwd_bf16 (dy formed on load, rounded to bf16 for the
-        MFMA and for dy_out; the input BatchNorm's partials over the stored dx)."""
+    def _wgrad(self, dy):
         x = self.X
         N, C, H, W = x.shape
-        K = self.num_filters
+        K, s = self.num_filters, self.stride
         OH, OW = self.out_hw
-        dx = empty_nhwc(N, C, OH, OW, x.dtype)
         bn = self._bn_in
-        res = residual_operand(residual, dx)
-        if residual is not None and res is None:
-            raise NotImplementedError("{}: bf16 residual must be a bf16 NHWC tensor".format(self.layer_name))
-        part = None
-        if bn is not None:
-            rows = lib.dk_pwconv_dgrad_bnbwd_bf16_stats_rows(N, OH, OW, K, C)
-            part = torch.empty((rows, 2, C), dtype=torch.float64, device=dx.device)
-        tok = bn.arm_partials(part) if bn is not None else None
-        r = lib.dk_pwconv_dgrad_bnbwd_bf16(to_nhwc(bg.g).data_ptr(), bg.x.data_ptr(), N, OH, OW, K, *bg.bnbwd_args(),
-                                           dy_out.data_ptr(), self.learned_params["weights"].data_ptr(), C,
-                                           dx.data_ptr(), ptr(res),
-                                           *((bn.x.data_ptr(), *bn.bn_args(), part.data_ptr()) if bn is not None
-                                             else (0, 0, 0, 0, 0, 0, 0)), st)
-        if bn is not None:
-            bn.hand_backward_partials(dx, part, r, tok)
-        return dx
+        nb = lib.dk_pwconv_wgrad_workspace_bytes(N, OH, OW, K, C)
 
-    def _wgrad(self, dy, x, N, H, W, C, K, s, OH, OW, P, w, bf):
-        # the weight gradient runs on the side stream (_hip.weight_grad_stream)
-        with weight_grad_stream(dy, x, *self._bn_tensors()):
-            sst = stream_handle()
-            if self.with_bias:
-                gb = grad_buffer(self, "bias", (K,))
-                nb = lib.dk_colsum_workspace_bytes(P, K)
-                lib.dk_colsum_f32(dy.data_ptr(), P, K, gb.data_ptr(), workspace.get(nb), nb, sst)
-            gw = grad_buffer(self, "weights", (K, C))
-            l2s = l2_strength(self.weight_regulariser)
-            nb = lib.dk_pwconv_wgrad_workspace_bytes(N, OH, OW, K, C)
-            if bf:
-                lib.dk_pwconv_wgrad_bnx_bf16(
-                    dy.data_ptr(), x.data_ptr(), N, H, W, C, K, s, OH, OW, w.data_ptr() if l2s else 0, l2s or 0.0,
-                    gw.data_ptr(), workspace.get(nb), nb,
-                    *(self._bn_in.bn_args() if self._bn_in is not None else (0, 0, 0, 0, 0)), sst)
-            elif self._bn_in is not None:
-                lib.dk_pwconv_wgrad_bnx_f32(dy.data_ptr(), x.data_ptr(), N, H, W, C, K, s, OH, OW,
-                                            w.data_ptr() if l2s else 0, l2s or 0.0, gw.data_ptr(), workspace.get(nb),
-                                            nb, *self._bn_in.bn_args(), sst)
+        def launch(wl2, l2s, gw, sst):
+            args = (dy.data_ptr(), x.data_ptr(), N, H, W, C, K, s, OH, OW, wl2, l2s, gw, workspace.get(nb), nb)
+            if x.dtype == BF16:
+                lib.dk_pwconv_wgrad_bnx_bf16(*args, *bn_args(bn), sst)
+            elif bn is not None:
+                lib.dk_pwconv_wgrad_bnx_f32(*args, *bn.bn_args(), sst)
             else:
-                lib.dk_pwconv_wgrad_f32(dy.data_ptr(), x.data_ptr(), N, H, W, C, K, s, OH, OW,
-                                        w.data_ptr() if l2s else 0, l2s or 0.0, gw.data_ptr(), workspace.get(nb), nb,
-                                        sst)
-            if l2s is None:
-                add_regulariser_grad(gw, w, self.weight_regulariser)
+                lib.dk_pwconv_wgrad_f32(*args, sst)
+        weight_grad(self, dy, x, N * OH * OW, K, (K, C), launch)
 
     def _dgrad(self, dy, residual, st):
         x = self.X
@@ -452,40 +384,30 @@ class PointwiseConvLayer(Layer):
         dx = empty_nhwc(N, C, OH * s, OW * s, x.dtype)  # widened shape, pointwise_convolution.py:68-72
         bn = self._bn_in
         res = residual_operand(residual, dx)
+        entry, rows_query = _DGRAD_EX[x.dtype]
+        # the input BatchNorm's partials (stage 1 of its backward) ride on the dgrad epilogue when its
+        # grid is the (widened) dx grid
+        with_part = bn is not None and (OH * s, OW * s) == (H, W)
         if bf:
-            # the input BatchNorm's partials ride on the dgrad when its grid is the (widened) dx grid; a
-            # residual goes in the epilogue except beside partials at stride > 1 (the entry refuses that
+            # a residual goes in the epilogue except beside partials at stride > 1 (the entry refuses that
             # pair: off-lattice residual terms would need reducing), where it is added afterwards
-            with_part = bn is not None and (OH * s, OW * s) == (H, W)
             fused = res if (s == 1 or not with_part) else None
-            if with_part:
-                rows = lib.dk_pwconv_dgrad_bf16_stats_rows(N, OH, OW, K, C, s)
-                part = torch.empty((rows, 2, C), dtype=torch.float64, device=dx.device)
-                tok = bn.arm_partials(part)
-                r = lib.dk_pwconv_dgrad_ex_bf16(dy.data_ptr(), N, OH, OW, K, w.data_ptr(), C, s, dx.data_ptr(),
-                                                ptr(fused), bn.x.data_ptr(), *bn.bn_args(), part.data_ptr(), st)
-                bn.hand_backward_partials(dx, part, r, tok)
-            else:
-                lib.dk_pwconv_dgrad_ex_bf16(dy.data_ptr(), N, OH, OW, K, w.data_ptr(), C, s, dx.data_ptr(), ptr(fused),
-                                            0, 0, 0, 0, 0, 0, 0, st)
-            if residual is not None and fused is None:
-                dx = add_residual(dx, residual)  # (a new tensor: the BN then recomputes its sums)
-            return dx
-        if bn is not None and (OH * s, OW * s) == (H, W) and (res is None or s == 1):
-            # + stage 1 of the input BatchNorm's backward, in the dgrad epilogue
-            rows = lib.dk_pwconv_dgrad_stats_rows(N, OH, OW, K, C)
-            part = torch.empty((rows, 2, C), dtype=torch.float64, device=dx.device)
-            tok = bn.arm_partials(part)
-            r = lib.dk_pwconv_dgrad_ex_f32(dy.data_ptr(), N, OH, OW, K, w.data_ptr(), C, s, dx.data_ptr(), ptr(res),
-                                           bn.x.data_ptr(), *bn.bn_args(), part.data_ptr(), st)
-            bn.hand_backward_partials(dx, part, r, tok)
-        elif res is not None:
-            lib.dk_pwconv_dgrad_ex_f32(dy.data_ptr(), N, OH, OW, K, w.data_ptr(), C, s, dx.data_ptr(), res.data_ptr(),
-                                       0, 0, 0, 0, 0, 0, 0, st)
+            added = fused is not None
+        else:
+            # fp32 keeps a fusable residual at stride > 1 and drops the partials instead
+            with_part = with_part and (res is None or s == 1)
+            fused = res
+            added = with_part or res is not None
+        if bf or with_part or res is not None:
+            pbn = bn if with_part else None
+            part = Partials(pbn, rows_query(N, OH, OW, K, C, s) if with_part else 0, C, dx.device)
+            r = getattr(lib, entry)(dy.data_ptr(), N, OH, OW, K, w.data_ptr(), C, s, dx.data_ptr(), ptr(fused),
+                                    pbn.x.data_ptr() if with_part else 0, *bn_args(pbn), part.ptr, st)
+            part.hand(dx, r)
         else:
             lib.dk_pwconv_dgrad_f32(dy.data_ptr(), N, OH, OW, K, w.data_ptr(), C, s, dx.data_ptr(), st)
-            if residual is not None:
-                dx = add_residual(dx, residual)
+        if residual is not None and not added:
+            dx = add_residual(dx, residual)  # (a new tensor: the BN then recomputes its sums)
         return dx
 
     def save_to_h5(self, open_f, save_grads=True):

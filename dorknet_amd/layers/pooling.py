@@ -19,6 +19,11 @@ from .._tensor import BF16, act_dtype, empty_nhwc, rows, to_nhwc
 from ._bn_input import BNOut, JoinOut, lattice_tag
 from .layer import Layer
 
+# per storage type: the pooling backward; the max-pool forward (plain, BatchNorm on load)
+_GAP_BWD = {torch.float32: "dk_gap_bwd_f32", BF16: "dk_gap_bwd_bf16"}
+_MAXPOOL_FWD = {torch.float32: ("dk_maxpool_fwd_f32", "dk_maxpool_fwd_bnx_f32"),
+                BF16: ("dk_maxpool_fwd_bf16", "dk_maxpool_fwd_bnx_bf16")}
+
 
 class GlobalAveragePoolingLayer(Layer):
     """
@@ -73,7 +78,7 @@ class GlobalAveragePoolingLayer(Layer):
         H, W = self.spatial_shape
         bf = getattr(self, "_in_dtype", torch.float32) == BF16
         dx = empty_nhwc(N, C, H, W, BF16 if bf else torch.float32)
-        (lib.dk_gap_bwd_bf16 if bf else lib.dk_gap_bwd_f32)(dy.data_ptr(), N, H * W, C, dx.data_ptr(), stream_handle())
+        getattr(lib, _GAP_BWD[dx.dtype])(dy.data_ptr(), N, H * W, C, dx.data_ptr(), stream_handle())
         return dx
 
     def save_to_h5(self, open_f, save_grads=True):
@@ -123,7 +128,6 @@ class MaxPoolLayer(Layer):
         OH, OW = H // s, W // s
         if OH < 1 or OW < 1:
             raise ValueError("MaxPoolLayer({}): a {}x{} input has no {}x{} window".format(self.layer_name, H, W, s, s))
-        bf = x.dtype == BF16
         y = empty_nhwc(N, C, OH, OW, x.dtype)
         if test_mode:
             idx = None
@@ -132,12 +136,11 @@ class MaxPoolLayer(Layer):
             idx = torch.empty((N, C, OH, OW), dtype=torch.uint8, device=x.device, memory_format=torch.channels_last)
             self.max_locs, self._in_shape, self._in_dtype = idx, (N, C, H, W), x.dtype
         ip = 0 if idx is None else idx.data_ptr()
+        plain, bnx = _MAXPOOL_FWD[x.dtype]
         if bn is not None:
-            fwd = lib.dk_maxpool_fwd_bnx_bf16 if bf else lib.dk_maxpool_fwd_bnx_f32
-            fwd(x.data_ptr(), N, H, W, C, s, *bn.bn_args(), y.data_ptr(), ip, stream_handle())
+            getattr(lib, bnx)(x.data_ptr(), N, H, W, C, s, *bn.bn_args(), y.data_ptr(), ip, stream_handle())
         else:
-            fwd = lib.dk_maxpool_fwd_bf16 if bf else lib.dk_maxpool_fwd_f32
-            fwd(x.data_ptr(), N, H, W, C, s, y.data_ptr(), ip, stream_handle())
+            getattr(lib, plain)(x.data_ptr(), N, H, W, C, s, y.data_ptr(), ip, stream_handle())
         return y
 
     def backward(self, upstream_dx):

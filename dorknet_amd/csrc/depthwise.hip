@@ -261,28 +261,30 @@ __global__ __launch_bounds__(256, JOIN ? 2 : 1) void dw_fwd_kernel(const T* __re
     const int own_r0 = oh0 * ST, own_r1 = oh1 * ST;
     // y = ReLU(bnA(a) + bnB(b)) for one window row from its raw operands; stored where this thread owns it
     auto join_row = [&](f32x4 (&dst)[NC], const f32x4* ra, const f32x4* rb, int ih) __attribute__((always_inline)) {
-      const bool rv = (unsigned)ih < (unsigned)H;
-      const bool own = rv && ih >= own_r0 && ih < own_r1;
+      if constexpr (JOIN) {  // (jtab has its eight rows in these instantiations only)
+        const bool rv = (unsigned)ih < (unsigned)H;
+        const bool own = rv && ih >= own_r0 && ih < own_r1;
 #pragma unroll
-      for (int q = 0; q < NC; ++q) {
-        const int iw = iw0 + q;
-        const bool ok = rv && (unsigned)iw < (unsigned)W;
-        f32x4 va = ra[q], vb = rb[q];
-        if (jf.ba.mean) va = bn_in4(va, jtab[0][cq], jtab[1][cq], jtab[2][cq], jtab[3][cq], jf.ba.relu);
-        if (jf.bb.mean) vb = bn_in4(vb, jtab[4][cq], jtab[5][cq], jtab[6][cq], jtab[7][cq], jf.bb.relu);
-        f32x4 v = va + vb;
-        uint32_t m = 0;
+        for (int q = 0; q < NC; ++q) {
+          const int iw = iw0 + q;
+          const bool ok = rv && (unsigned)iw < (unsigned)W;
+          f32x4 va = ra[q], vb = rb[q];
+          if (jf.ba.mean) va = bn_in4(va, jtab[0][cq], jtab[1][cq], jtab[2][cq], jtab[3][cq], jf.ba.relu);
+          if (jf.bb.mean) vb = bn_in4(vb, jtab[4][cq], jtab[5][cq], jtab[6][cq], jtab[7][cq], jf.bb.relu);
+          f32x4 v = va + vb;
+          uint32_t m = 0;
 #pragma unroll
-        for (int e = 0; e < 4; ++e) {
-          const bool pos = v[e] > 0.f;
-          v[e] = pos ? v[e] : 0.f;
-          m |= (uint32_t)pos << (8 * e);
-        }
-        dst[q] = ok ? v : f32x4{0.f, 0.f, 0.f, 0.f};
-        if (q >= 1 && q <= TW * ST && own && ok) {
-          const size_t e0 = ((size_t)(n * H + ih) * W + iw) * C + c;
-          st4(jf.y + e0, v);
-          if (jf.mask) *reinterpret_cast<uint32_t*>(jf.mask + e0) = m;
+          for (int e = 0; e < 4; ++e) {
+            const bool pos = v[e] > 0.f;
+            v[e] = pos ? v[e] : 0.f;
+            m |= (uint32_t)pos << (8 * e);
+          }
+          dst[q] = ok ? v : f32x4{0.f, 0.f, 0.f, 0.f};
+          if (q >= 1 && q <= TW * ST && own && ok) {
+            const size_t e0 = ((size_t)(n * H + ih) * W + iw) * C + c;
+            st4(jf.y + e0, v);
+            if (jf.mask) *reinterpret_cast<uint32_t*>(jf.mask + e0) = m;
+          }
         }
       }
     };
@@ -862,9 +864,9 @@ struct BnBwdOut {  // the BatchNorm after this layer: dy = bn_bwd_elem(x1, g)
 // half the LDS reads, the bound of the one-column form on bf16 (twice the elements per byte).
 // RES: a residual addend may be given (false: none -- its loads and widening are compiled out).
 // JM (JOIN): the join's ReLU mask bytes may be given (false: the mask is y > 0, no mask loads).
-template <bool BNX, bool STATS, bool RELU1, bool JOIN = false, class T = float, int CPT = 1, int NT = 256,
-          bool RES = true, bool JM = true>
-__global__ __launch_bounds__(NT, NT == 64 ? 2 : 1) void dw_bwd_fused_kernel(const T* __restrict__ g, const T* __restrict__ x1,
+template <bool BNX, bool STATS, bool RELU1, bool JOIN = false, class T = float, int CPT = 1, bool RES = true,
+          bool JM = true>
+__global__ __launch_bounds__(256, 1) void dw_bwd_fused_kernel(const T* __restrict__ g, const T* __restrict__ x1,
                                                            uint32_t bytes, BnBwdOut ob, const T* __restrict__ x,
                                                            BnIn bn, const float* __restrict__ w_crs,
                                                            T* __restrict__ dx, const T* __restrict__ res,
@@ -876,6 +878,7 @@ __global__ __launch_bounds__(NT, NT == 64 ? 2 : 1) void dw_bwd_fused_kernel(cons
   static_assert(!STATS || BNX, "input-BN partials need the input BN");
   static_assert(!(JOIN && (STATS || BNX)), "the join's partials replace the input BN's");
   constexpr bool PART = STATS || JOIN;
+  constexpr int NT = 256;                // threads per block
   const int CP = CL / CPT;               // threads per channel group
   const int CG = NT / CP;                // channel groups per block
   const int NI = (CL + 2) * CG;         // dy float4s per LDS row (with the 1-column halos)
@@ -914,7 +917,7 @@ __global__ __launch_bounds__(NT, NT == 64 ? 2 : 1) void dw_bwd_fused_kernel(cons
   const __amdgpu_buffer_rsrc_t rjm = make_rsrc_v(JOIN ? jn.mask : nullptr, (JOIN && jn.mask) ? bytes / 4u : 0u);
   // the per-channel BatchNorm terms and the (flipped) filters live in LDS, read where used:
   // held in registers they kept the kernel at 2 waves per SIMD, too few to hide a row's loads
-  __shared__ f32x4 ptab[13 + RS][NT == 64 ? 16 : 32];  // [term][channel group]; CG <= 32 (16: dwb_geom)
+  __shared__ f32x4 ptab[13 + RS][32];  // [term][channel group]; CG <= 32 (dwb_geom)
   for (int i = tid; i < 13 * CG; i += NT) {
     const int t = i / CG, q = i - t * CG;
     const int cc = (cht * CG + q) * 4;
@@ -1630,45 +1633,47 @@ __global__ __launch_bounds__(256, 2) void dw_bwd_s2_kernel(const T* __restrict__
   }
 }
 
-// Block geometry of the fused stride-1 backward: CG channel groups of 4 x CL / CPT column lanes
-// (CG * CL / CPT = 256 threads), a CL-column strip.  One column per thread: 16 columns x 64
-// channels, or 8 x 128 for narrow images; fewer channel groups (wider strips) when C / 4 has no
-// such factor.  Two columns per thread (knob kind 21; W >= 12): CG in {16, 32}
-// with the strip width (32 or 16 columns) that pads the row least, ties to the wider.  fp32 and bf16
-// alike: 512 x 56 x 56 x 64 bf16 328 -> 284 us, 256 x 56 x 56 x 64 fp32 205 -> 182 us (dwb_bench.py).
-struct DwbGeom {
-  int cpt, cl, cg, nt;
-};
-static inline DwbGeom dwb_geom(int W, int C, int cpt, int nt = 256) {
-  const int C4 = C / 4;
-  if (cpt == 2 && W >= 12 && C4 % 16 == 0) {
-    const int pad32 = (W + 31) / 32 * 32 - W, pad16 = (W + 15) / 16 * 16 - W;
-    if (C4 % 32 == 0 && pad16 < pad32) return DwbGeom{2, 16, 32, 256};
-    return DwbGeom{2, 32, 16, 256};
-  }
-  int cg = W > 8 ? 16 : 32;
-  while (cg > 1 && C4 % cg) cg >>= 1;
-  return DwbGeom{1, 256 / cg, cg, 256};
+// ---------------------------------------------------------------------------------------
+// Host side, part 1: argument checks and plans.  A plan is the one place where a launch's grid,
+// its rows of partial sums and its workspace are computed: the row / workspace queries and the
+// launchers below both read it.
+// ---------------------------------------------------------------------------------------
+static inline bool fits(size_t bytes) { return bytes < ((size_t)1 << 31); }
+// every pointer a multiple of `a` bytes (a power of two).  Null passes: an optional operand left out
+template <class... P>
+static inline bool aligned(size_t a, const P*... p) {
+  return ((reinterpret_cast<uintptr_t>(p) | ...) & (a - 1)) == 0;
 }
-static inline int dwb_cpt(size_t) { return knob(kKnobDwbCols) == 2 ? 2 : 1; }
-static inline int dwb_nt(size_t) { return 256; }
-// Image runs of the fused stride-1 backward: one image per block while N * column strips * channel
-// tiles blocks fit knob kind 7 (default 768 = three resident blocks per CU: its LDS and
-// registers allow three); above that the batch is dealt into runs so the grid is one round (a
-// second, partial round of blocks cost small images up to twice the time: 7 x 7 x 512 ran 1024
-// one-image blocks).  0 = one image per block always.
-static inline int dwb_target_blocks() { return knob(kKnobDwbBlocks); }  // kind 7
-static inline int dwb_nranges(int N, int W, int C, const DwbGeom& g) {
-  const int per_image = ((W + g.cl - 1) / g.cl) * ((C / 4) / g.cg);
-  // the two-column form holds two blocks per CU (its registers; eight one-wave blocks), the
-  // one-column form three
-  const int t = g.cpt == 2 ? dwb_target_blocks() * 2 / 3 * (256 / g.nt) : dwb_target_blocks();
-  if (t <= 0 || (long long)N * per_image <= t) return N;
-  const int r = t / per_image;
-  return r < 1 ? 1 : (r > N ? N : r);
+template <class... P>
+static inline bool aligned16(const P*... p) {
+  return aligned(16, p...);
 }
-static inline int dwb_strips(int N, int W, int C, const DwbGeom& g) {
-  return dwb_nranges(N, W, C, g) * ((W + g.cl - 1) / g.cl);
+template <class... P>
+static inline bool all_set(const P*... p) {
+  return (... && (p != nullptr));
+}
+static inline bool bn_ok(const BnIn& bn) {
+  return !bn.mean || (all_set(bn.invstd, bn.gamma, bn.beta) && aligned16(bn.mean, bn.invstd, bn.gamma, bn.beta));
+}
+// Partial rows (statistics, BN-backward sums) of the forward and sub-pixel kernels: a block must
+// cover every channel, so C / 4 divides 256
+static inline bool dw_rows_ok(int C) { return C % 4 == 0 && C / 4 <= 256 && 256 % (C / 4) == 0; }
+
+// Blocks of dw_fwd_kernel, one row of partials each: a thread takes 4 channels of TW output
+// columns of one segment of output rows; bf16 storage slides down whole columns (dw_fwd_seg)
+static long long dw_fwd_blocks(int N, int OH, int OW, int C, int stride, size_t elem_bytes) {
+  const int TW = stride == 1 ? DwTile<1>::TW : DwTile<2>::TW, SEG = dw_fwd_seg(OH, elem_bytes == 2);
+  return cdivll((long long)N * ((OH + SEG - 1) / SEG) * ((OW + TW - 1) / TW) * (C / 4), 256);
+}
+static int dw_fwd_rows(int N, int OH, int OW, int C, int stride, size_t elem_bytes) {
+  return dw_rows_ok(C) ? (int)dw_fwd_blocks(N, OH, OW, C, stride, elem_bytes) : 0;
+}
+
+// The geometries dw_dgrad_subpixel_kernel is built for, and its blocks (one row of join / BN
+// partials each): a thread takes 4 channels of 4 consecutive quads of dx
+#define DW_SUBPIX_CASES(X) X(3, 3, 2, 1) X(5, 5, 2, 2) X(1, 1, 2, 0)
+static inline long long dw_subpix_blocks(int N, int H, int W, int C, int stride) {
+  return cdivll((long long)N * cdiv(H, stride) * cdiv(cdiv(W, stride), 4) * (C / 4), 256);
 }
 
 static int dw_wgrad_blocks(int N, int OH, int OW, int C) {
@@ -1681,19 +1686,83 @@ static int dw_wgrad_blocks(int N, int OH, int OW, int C) {
   return nblk;
 }
 
-static inline bool fits(size_t bytes) { return bytes < ((size_t)1 << 31); }
-static inline bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
-static inline bool bn_ok(const BnIn& bn) {
-  return !bn.mean || (bn.invstd && bn.gamma && bn.beta && aligned16(bn.mean) && aligned16(bn.invstd) &&
-                      aligned16(bn.gamma) && aligned16(bn.beta));
+// Block geometry of the fused stride-1 backward: CG channel groups of 4 x CL / CPT column lanes
+// (CG * CL / CPT = 256 threads), a CL-column strip.  One column per thread: 16 columns x 64
+// channels, or 8 x 128 for narrow images; fewer channel groups (wider strips) when C / 4 has no
+// such factor.  Two columns per thread (knob kind 21; W >= 12): CG in {16, 32}
+// with the strip width (32 or 16 columns) that pads the row least, ties to the wider.  fp32 and bf16
+// alike: 512 x 56 x 56 x 64 bf16 328 -> 284 us, 256 x 56 x 56 x 64 fp32 205 -> 182 us (dwb_bench.py).
+struct DwbGeom {
+  int cpt, cl, cg;
+};
+static inline DwbGeom dwb_geom(int W, int C, int cpt) {
+  const int C4 = C / 4;
+  if (cpt == 2 && W >= 12 && C4 % 16 == 0) {
+    const int pad32 = (W + 31) / 32 * 32 - W, pad16 = (W + 15) / 16 * 16 - W;
+    if (C4 % 32 == 0 && pad16 < pad32) return DwbGeom{2, 16, 32};
+    return DwbGeom{2, 32, 16};
+  }
+  int cg = W > 8 ? 16 : 32;
+  while (cg > 1 && C4 % cg) cg >>= 1;
+  return DwbGeom{1, 256 / cg, cg};
+}
+// The fused stride-1 backward's launch: geometry, image runs, partial rows (strips = image runs x
+// column strips; the grid is strips x ncht channel tiles) and dynamic LDS.  The same for fp32 and
+// bf16 storage.
+// Image runs: one image per block while N * column strips * channel tiles blocks fit knob kind 7
+// (default 768 = three resident blocks per CU: its LDS and registers allow three); above that the
+// batch is dealt into runs so the grid is one round (a second, partial round of blocks cost small
+// images up to twice the time: 7 x 7 x 512 ran 1024 one-image blocks).  0 = one image per block
+// always.
+struct DwbPlan {
+  DwbGeom geo;
+  int nranges, strips, ncht;
+  size_t shm;
+  size_t ws_bytes(int C, int R, int S) const { return (size_t)strips * C * R * S * sizeof(float); }
+};
+static DwbPlan dwb_plan(int N, int W, int C) {
+  DwbPlan p;
+  p.geo = dwb_geom(W, C, knob(kKnobDwbCols) == 2 ? 2 : 1);
+  const int nct = (W + p.geo.cl - 1) / p.geo.cl;
+  p.ncht = (C / 4) / p.geo.cg;
+  const int per_image = nct * p.ncht;
+  // the two-column form holds two blocks per CU (its registers), the one-column form three
+  const int t = p.geo.cpt == 2 ? knob(kKnobDwbBlocks) * 2 / 3 : knob(kKnobDwbBlocks);
+  p.nranges = N;
+  if (t > 0 && (long long)N * per_image > t) p.nranges = std::min(std::max(t / per_image, 1), N);
+  p.strips = p.nranges * nct;
+  // the weight-gradient reduction, or the two-row dy ring if that is larger (36 KiB at the most)
+  p.shm = std::max((size_t)256 * 9 * 4 * sizeof(float), (size_t)2 * (p.geo.cl + 2) * p.geo.cg * sizeof(f32x4));
+  return p;
+}
+// (the queries answer 0 for a channel count the entry points refuse)
+static int dwb_rows(int N, int W, int C) { return (C < 4 || C % 4) ? 0 : dwb_plan(N, W, C).strips; }
+static size_t dwb_ws_bytes(int N, int W, int C, int R, int S) {
+  return (C < 4 || C % 4) ? 0 : dwb_plan(N, W, C).ws_bytes(C, R, S);
 }
 
-template <int ST>
-static long long dw_fwd_threads(int N, int OH, int OW, int C, bool whole) {
-  constexpr int TW = DwTile<ST>::TW;
-  const int SEG = dw_fwd_seg(OH, whole);
-  return (long long)N * ((OH + SEG - 1) / SEG) * ((OW + TW - 1) / TW) * (C / 4);
+// The fused stride-2 backward's launch: blocks of 256 / (C / 4) items (image, quad row, segment of
+// two quad columns) walked with the grid's stride, one row of partials per block
+static bool dws2_ok(int N, int H, int W, int C, int OH, int OW) {
+  return N >= 1 && H >= 1 && W >= 1 && C >= 4 && C % 4 == 0 && 256 % (C / 4) == 0 && OH == (H + 1) / 2 &&
+         OW == (W + 1) / 2;
 }
+static int dws2_blocks(int N, int H, int W, int C) {
+  const int C4 = C / 4, IPB = 256 / C4;
+  const long long items = (long long)N * ((H + 1) / 2) * ((((W + 1) / 2) + 1) / 2);
+  long long b = (items + IPB - 1) / IPB;
+  const int target = knob(kKnobDwbBlocks) * 2 / 3;  // two resident blocks per CU
+  if (target > 0 && b > target) b = target;
+  return b < 1 ? 1 : (int)b;
+}
+static int dws2_rows(int N, int H, int W, int C) {
+  return dws2_ok(N, H, W, C, (H + 1) / 2, (W + 1) / 2) ? dws2_blocks(N, H, W, C) : 0;
+}
+static size_t dws2_ws_bytes(int rows, int C) { return (size_t)rows * C * 9 * sizeof(float); }
+
+// ---------------------------------------------------------------------------------------
+// Host side, part 2: the launchers, one per kernel family, templated on the storage type.
+// ---------------------------------------------------------------------------------------
 
 // part: per-block sums (mode 1: output statistics; mode 2 with xo/obn: BN-backward sums).
 // wl: weight layout (load_dw_weights).  Only the combinations the entry points use exist.
@@ -1702,39 +1771,34 @@ static int launch_dw_fwd(const T* x, const float* wt, const float* bias, T* y, i
                          int OW, int pad, const BnIn& bn, double* part, const T* xo, const BnIn& obn, int wl,
                          const T* res, hipStream_t st, const JoinFwd* jn = nullptr) {
   const uint32_t xb = (uint32_t)((size_t)N * H * W * C * sizeof(T));
-  constexpr bool whole = sizeof(T) == 2;
-  const dim3 grid((unsigned)cdivll(dw_fwd_threads<ST>(N, OH, OW, C, whole), 256));
+  const dim3 grid((unsigned)dw_fwd_blocks(N, OH, OW, C, ST, sizeof(T)));
   FoldTail ft;  // an armed in-launch fold of the partial rows (fold_tail.h)
   if (!part || !fold_take(part, (int)grid.x, C, 1, &ft)) ft.part = nullptr;
   const JoinFwd jf = jn ? *jn : JoinFwd{};
-  if constexpr (R == 3 && S == 3 && sizeof(T) == 4) {
-    if (jn) {
-      // the residual join formed on load (JOIN): reference-layout filters, no input BN
-      if (wl != 1 || bn.mean || xo || pad != 1) return DK_ERR_ARGS;
-      if (part)
-        hipLaunchKernelGGL((dw_fwd_kernel<R, S, ST, false, false, 1, 1, T, true>), grid, dim3(256), 0, st, x, xb, wt,
-                           bias, y, N, H, W, C, OH, OW, pad, bn, part, xo, obn, res, ft, nt_stores(kNtDwFwd),
-                           dw_fwd_seg(OH, whole), jf);
-      else
-        hipLaunchKernelGGL((dw_fwd_kernel<R, S, ST, false, false, 0, 1, T, true>), grid, dim3(256), 0, st, x, xb, wt,
-                           bias, y, N, H, W, C, OH, OW, pad, bn, part, xo, obn, res, ft, nt_stores(kNtDwFwd),
-                           dw_fwd_seg(OH, whole), jf);
-      return fold_status(launch_status(), ft);
-    }
-  }
-  if (jn) return DK_ERR_ARGS;
-#define DW_LAUNCH1(B, RL, ST_, WL_)                                                                                  \
-  hipLaunchKernelGGL((dw_fwd_kernel<R, S, ST, B, RL, ST_, WL_, T>), grid, dim3(256), 0, st, x, xb, wt, bias, y, N, H, \
-                     W, C, OH, OW, pad, bn, part, xo, obn, res, ft, nt_stores(kNtDwFwd), dw_fwd_seg(OH, whole), jf)
-#define DW_LAUNCH(B, ST_, WL_)            \
-  do {                                    \
-    if (B && bn.relu)                     \
-      DW_LAUNCH1(B, B, ST_, WL_);         \
-    else                                  \
-      DW_LAUNCH1(B, false, ST_, WL_);     \
+#define DW_LAUNCH1(B, RL, ST_, WL_, JOIN_)                                                                           \
+  hipLaunchKernelGGL((dw_fwd_kernel<R, S, ST, B, RL, ST_, WL_, T, JOIN_>), grid, dim3(256), 0, st, x, xb, wt, bias, y, \
+                     N, H, W, C, OH, OW, pad, bn, part, xo, obn, res, ft, nt_stores(kNtDwFwd),                       \
+                     dw_fwd_seg(OH, sizeof(T) == 2), jf)
+#define DW_LAUNCH(B, ST_, WL_)               \
+  do {                                       \
+    if (B && bn.relu)                        \
+      DW_LAUNCH1(B, B, ST_, WL_, false);     \
+    else                                     \
+      DW_LAUNCH1(B, false, ST_, WL_, false); \
   } while (0)
   const int mode = part ? (xo ? 2 : 1) : 0;
-  if (wl == 0 && !bn.mean && mode == 0)
+  if (jn) {
+    // the residual join formed on load (JOIN): 3 x 3 fp32, reference-layout filters, no input BN
+    if constexpr (R == 3 && S == 3 && sizeof(T) == 4) {
+      if (wl != 1 || bn.mean || xo || pad != 1) return DK_ERR_ARGS;
+      if (part)
+        DW_LAUNCH1(false, false, 1, 1, true);
+      else
+        DW_LAUNCH1(false, false, 0, 1, true);
+    } else {
+      return DK_ERR_ARGS;
+    }
+  } else if (wl == 0 && !bn.mean && mode == 0)
     DW_LAUNCH(false, 0, 0);
   else if (wl == 0 && bn.mean && mode == 0)
     DW_LAUNCH(true, 0, 0);
@@ -1763,8 +1827,8 @@ static int dw_fwd_dispatch(const T* x, const float* wt, const float* bias, T* y,
                            double* part = nullptr, const T* xo = nullptr, const BnIn& obn = BnIn{}, int wl = 0,
                            const T* res = nullptr, const JoinFwd* jn = nullptr) {
   if (res && (!aligned16(res) || wl != 2)) return DK_ERR_ARGS;  // residual addend: dgrad only
-  if (C % 4 || !aligned16(x) || !aligned16(wt) || !fits((size_t)N * H * W * C * 4) || !bn_ok(bn)) return DK_ERR_ARGS;
-  if (part && (C / 4 > 256 || 256 % (C / 4))) return DK_ERR_ARGS;
+  if (C % 4 || !aligned16(x, wt) || !fits((size_t)N * H * W * C * 4) || !bn_ok(bn)) return DK_ERR_ARGS;
+  if (part && !dw_rows_ok(C)) return DK_ERR_ARGS;
   if (xo && (bn.mean || !obn.mean || !aligned16(xo) || !bn_ok(obn))) return DK_ERR_ARGS;
 #define DW_CASE(RR, SS, STR)                                                                     \
   if (R == RR && S == SS && stride == STR)                                                           \
@@ -1779,197 +1843,82 @@ static int dw_fwd_dispatch(const T* x, const float* wt, const float* bias, T* y,
   return DK_ERR_ARGS;
 }
 
-template <class T>
-static int dw_wgrad(const T* dy, const T* x, int N, int H, int W, int C, int R, int S, int stride, int pad, int OH,
-                    int OW, const float* w_crs, float l2, float* dw_crs, void* ws, size_t ws_bytes, const BnIn& bn,
-                    hipStream_t st);
-
-}  // namespace dk
-
-using namespace dk;
-
-DK_API int dk_dw_weight_rsc_f32(const float* w_crs, int C, int R, int S, float* w_rsc, void* stream) {
-  const int total = C * R * S;
-  hipLaunchKernelGGL(dw_weight_rsc_kernel, dim3(cdiv(total, 256)), dim3(256), 0, as_stream(stream), w_crs, C, R, S, 0,
-                     w_rsc);
-  return launch_status();
-}
-
-DK_API int dk_dwconv_fwd_f32(const float* x, int N, int H, int W, int C, const float* w_rsc, int R, int S, int stride,
-                             int pad, const float* bias, float* y, int OH, int OW, void* stream) {
-  return dw_fwd_dispatch(x, w_rsc, bias, y, N, H, W, C, R, S, stride, OH, OW, pad, BnIn{}, as_stream(stream));
-}
-
-DK_API int dk_dwconv_fwd_bnx_f32(const float* x, int N, int H, int W, int C, const float* w_rsc, int R, int S,
-                                 int stride, int pad, const float* bias, float* y, int OH, int OW,
-                                 const float* bn_mean, const float* bn_invstd, const float* bn_gamma,
-                                 const float* bn_beta, int bn_relu, void* stream) {
-  if (!bn_mean) return DK_ERR_ARGS;
-  return dw_fwd_dispatch(x, w_rsc, bias, y, N, H, W, C, R, S, stride, OH, OW, pad,
-                         BnIn{bn_mean, bn_invstd, bn_gamma, bn_beta, bn_relu}, as_stream(stream));
-}
-
-// Rows of BatchNorm partial statistics dk_dwconv_fwd_ex_f32 writes; 0 = statistics not
-// supported for this channel count (C/4 must divide 256).
-static int dw_fwd_stats_rows(int N, int OH, int OW, int C, int stride, bool whole) {
-  if (C % 4 || C / 4 > 256 || 256 % (C / 4)) return 0;
-  const long long thr =
-      stride == 1 ? dw_fwd_threads<1>(N, OH, OW, C, whole) : dw_fwd_threads<2>(N, OH, OW, C, whole);
-  return (int)cdivll(thr, 256);
-}
-DK_API int dk_dwconv_fwd_stats_rows(int N, int OH, int OW, int C, int stride) {
-  return dw_fwd_stats_rows(N, OH, OW, C, stride, false);
-}
-// The bf16 forward's rows (dk_dwconv_fwd_ex_bf16: whole output columns per thread, fewer blocks).
-DK_API int dk_dwconv_fwd_bf16_stats_rows(int N, int OH, int OW, int C, int stride) {
-  return dw_fwd_stats_rows(N, OH, OW, C, stride, true);
-}
-
-// Reads the filters in the reference layout W[C][R][S] (no re-layout copy).
-DK_API int dk_dwconv_fwd_ex_f32(const float* x, int N, int H, int W, int C, const float* w_crs, int R, int S,
-                                int stride, int pad, const float* bias, float* y, int OH, int OW,
-                                const float* bn_mean, const float* bn_invstd, const float* bn_gamma,
-                                const float* bn_beta, int bn_relu, double* stats, void* stream) {
-  if (stride != 1 && stride != 2) return DK_ERR_ARGS;
-  return dw_fwd_dispatch<float>(x, w_crs, bias, y, N, H, W, C, R, S, stride, OH, OW, pad,
-                         BnIn{bn_mean, bn_invstd, bn_gamma, bn_beta, bn_relu}, as_stream(stream), stats, nullptr,
-                         BnIn{}, 1);
-}
-
-// The layer's input is the residual join y = ReLU(bnA(a) + bnB(b)) (dk_bn_add_f32's operands), formed
-// as the window is loaded and stored once into y_join (+ its ReLU mask, nullable); the rest as
-// dk_dwconv_fwd_ex_f32 without an input BatchNorm.  3 x 3 filters, pad 1, stride 1 or 2.
-DK_API int dk_dwconv_fwd_join_f32(const float* a, const float* a_mean, const float* a_invstd, const float* a_gamma,
-                                  const float* a_beta, int a_relu, const float* b, const float* b_mean,
-                                  const float* b_invstd, const float* b_gamma, const float* b_beta, int b_relu,
-                                  float* y_join, uint8_t* mask, int N, int H, int W, int C, const float* w_crs,
-                                  int stride, const float* bias, float* y, int OH, int OW, double* stats,
-                                  void* stream) {
-  if (stride != 1 && stride != 2) return DK_ERR_ARGS;
-  const JoinFwd jf{b, BnIn{a_mean, a_invstd, a_gamma, a_beta, a_relu}, BnIn{b_mean, b_invstd, b_gamma, b_beta, b_relu},
-                   y_join, mask};
-  if (!b || !y_join || !aligned16(b) || !aligned16(y_join) || !bn_ok(jf.ba) || !bn_ok(jf.bb) || C > 512) return DK_ERR_ARGS;
-  if (mask && (reinterpret_cast<uintptr_t>(mask) & 3)) return DK_ERR_ARGS;
-  return dw_fwd_dispatch<float>(a, w_crs, bias, y, N, H, W, C, 3, 3, stride, OH, OW, 1, BnIn{}, as_stream(stream),
-                                stats, nullptr, BnIn{}, 1, nullptr, &jf);
-}
-
-// w_rsc is the (unflipped) [R][S][C] copy; stride-1 dgrad flips it internally into ws.
-DK_API size_t dk_dwconv_dgrad_workspace_bytes(int C, int R, int S) { return (size_t)C * R * S * sizeof(float); }
-
 // Input gradient.  res (optional): added to dx (the residual join's other gradient term);
 // bn_x/obn/part (optional, stride 1 only): + stage 1 of the backward of the BatchNorm whose
-// output the layer consumed.
+// output the layer consumed.  ws: C x R x S floats (the generic gather path's flipped filters).
 template <class T>
 static int dw_dgrad(const T* dy, int N, int OH, int OW, int C, const float* w_crs, int R, int S, int stride, int pad,
                     T* dx, int H, int W, void* ws, size_t ws_bytes, const T* res, const T* bn_x, const BnIn& obn,
                     double* part, hipStream_t st, const JoinBwd* jn = nullptr) {
   if (C % 4) return DK_ERR_ARGS;
-  if (ws_bytes < dk_dwconv_dgrad_workspace_bytes(C, R, S)) return DK_ERR_WORKSPACE;
+  if (ws_bytes < (size_t)C * R * S * sizeof(float)) return DK_ERR_WORKSPACE;
   float* wt = static_cast<float*>(ws);
   if (stride == 1 && pad <= R - 1 && pad <= S - 1 && R == S) {
     // dx = correlation of dy with the flipped filter (read flipped from W[C][R][S]), padding R-1-pad
-    if (part && dk_dwconv_fwd_stats_rows(N, H, W, C, 1) == 0) return DK_ERR_ARGS;
+    if (part && dw_fwd_rows(N, H, W, C, 1, sizeof(T)) == 0) return DK_ERR_ARGS;
     return dw_fwd_dispatch(dy, w_crs, nullptr, dx, N, OH, OW, C, R, S, 1, H, W, R - 1 - pad, BnIn{}, st,
                            part ? part : nullptr, part ? bn_x : nullptr, part ? obn : BnIn{}, 2, res);
   }
   JoinBwd bnj{};
   if (part && !jn) {
     // the input BatchNorm's stage-1 partials on the sub-pixel store (JoinBwd::bnmode)
-    if (!bn_x || !obn.mean || !obn.invstd || !obn.gamma || !obn.beta || (C / 4) > 256 || 256 % (C / 4))
+    if (!all_set(bn_x, obn.mean, obn.invstd, obn.gamma, obn.beta) || (C / 4) > 256 || 256 % (C / 4))
       return DK_ERR_ARGS;
     bnj = JoinBwd{nullptr, bn_x, obn.mean, obn.invstd, 0, obn.gamma, obn.beta, obn.relu, 1};
     jn = &bnj;
   }
-  if (!fits((size_t)N * OH * OW * C * 4) || !aligned16(dy) || !aligned16(dx) || !aligned16(w_crs) ||
-      (res && !aligned16(res)))
-    return DK_ERR_ARGS;
+  if (!fits((size_t)N * OH * OW * C * 4) || !aligned16(dy, dx, w_crs, res)) return DK_ERR_ARGS;
   const uint32_t gb = (uint32_t)((size_t)N * OH * OW * C * sizeof(T));
 #define DW_SUBPIX(RR, SS, STR, PD)                                                                                   \
   if (R == RR && S == SS && stride == STR && pad == PD) {                                                            \
-    const long long items = (long long)N * cdiv(H, STR) * cdiv(cdiv(W, STR), 4) * (C / 4);                         \
-    const dim3 grid((unsigned)cdivll(items, 256));                                                                   \
+    const dim3 grid((unsigned)dw_subpix_blocks(N, H, W, C, STR));                                                    \
     if (jn) {                                                                                                        \
       if (sizeof(T) != sizeof(float) && !jn->bnmode) return DK_ERR_ARGS; /* the join fusion: fp32 only */            \
       FoldTail ft;                                                                                                   \
       if (!fold_take(part, (int)grid.x, C, 1, &ft)) ft.part = nullptr;                                              \
       hipLaunchKernelGGL((dw_dgrad_subpixel_kernel<RR, SS, STR, PD, T, true>), grid, dim3(256), 0, st, dy, gb,      \
-                         w_crs, dx, N, H, W, C, OH, OW, res, *jn, part, ft, nt_stores(dgrad_nt_fam<T>()));                  \
+                         w_crs, dx, N, H, W, C, OH, OW, res, *jn, part, ft, nt_stores(dgrad_nt_fam<T>()));          \
       return fold_status(launch_status(), ft);                                                                       \
     }                                                                                                                \
     hipLaunchKernelGGL((dw_dgrad_subpixel_kernel<RR, SS, STR, PD, T>), grid, dim3(256), 0, st, dy, gb, w_crs, dx, N, \
-                       H, W, C, OH, OW, res, JoinBwd{}, nullptr, FoldTail{}, nt_stores(dgrad_nt_fam<T>()));                 \
+                       H, W, C, OH, OW, res, JoinBwd{}, nullptr, FoldTail{}, nt_stores(dgrad_nt_fam<T>()));         \
     return launch_status();                                                                                          \
   }
-  DW_SUBPIX(3, 3, 2, 1)
-  DW_SUBPIX(5, 5, 2, 2)
-  DW_SUBPIX(1, 1, 2, 0)
+  DW_SUBPIX_CASES(DW_SUBPIX)
 #undef DW_SUBPIX
   if (res || jn) return DK_ERR_ARGS;  // generic gather path: no residual / join fusion
   if constexpr (sizeof(T) != sizeof(float)) {
     return DK_ERR_ARGS;  // generic gather path: fp32 storage only
   } else {
-  hipLaunchKernelGGL(dw_weight_rsc_kernel, dim3(cdiv(C * R * S, 256)), dim3(256), 0, st, w_crs, C, R, S, 0, wt);
-  int rc = launch_status();
-  if (rc) return rc;
-  const long long total = (long long)N * H * W * (C / 4);
-  const dim3 grid((unsigned)cdivll(total, 256));
-  if (R == 3 && S == 3)
-    hipLaunchKernelGGL((dw_dgrad_gather_kernel<3, 3>), grid, dim3(256), 0, st, dy, wt, dx, N, H, W, C, OH, OW, stride,
-                       pad);
-  else if (R == 5 && S == 5)
-    hipLaunchKernelGGL((dw_dgrad_gather_kernel<5, 5>), grid, dim3(256), 0, st, dy, wt, dx, N, H, W, C, OH, OW, stride,
-                       pad);
-  else if (R == 1 && S == 1)
-    hipLaunchKernelGGL((dw_dgrad_gather_kernel<1, 1>), grid, dim3(256), 0, st, dy, wt, dx, N, H, W, C, OH, OW, stride,
-                       pad);
-  else
-    return DK_ERR_ARGS;
-  return launch_status();
+    hipLaunchKernelGGL(dw_weight_rsc_kernel, dim3(cdiv(C * R * S, 256)), dim3(256), 0, st, w_crs, C, R, S, 0, wt);
+    int rc = launch_status();
+    if (rc) return rc;
+    const long long total = (long long)N * H * W * (C / 4);
+    const dim3 grid((unsigned)cdivll(total, 256));
+    if (R == 3 && S == 3)
+      hipLaunchKernelGGL((dw_dgrad_gather_kernel<3, 3>), grid, dim3(256), 0, st, dy, wt, dx, N, H, W, C, OH, OW, stride,
+                         pad);
+    else if (R == 5 && S == 5)
+      hipLaunchKernelGGL((dw_dgrad_gather_kernel<5, 5>), grid, dim3(256), 0, st, dy, wt, dx, N, H, W, C, OH, OW, stride,
+                         pad);
+    else if (R == 1 && S == 1)
+      hipLaunchKernelGGL((dw_dgrad_gather_kernel<1, 1>), grid, dim3(256), 0, st, dy, wt, dx, N, H, W, C, OH, OW, stride,
+                         pad);
+    else
+      return DK_ERR_ARGS;
+    return launch_status();
   }
 }
 
-DK_API int dk_dwconv_dgrad_f32(const float* dy, int N, int OH, int OW, int C, const float* w_crs, int R, int S,
-                               int stride, int pad, float* dx, int H, int W, void* ws, size_t ws_bytes,
-                               void* stream) {
-  return dw_dgrad<float>(dy, N, OH, OW, C, w_crs, R, S, stride, pad, dx, H, W, ws, ws_bytes, nullptr, nullptr, BnIn{},
-                  nullptr, as_stream(stream));
-}
-
-DK_API int dk_dwconv_dgrad_stats_rows(int N, int H, int W, int C, int stride) {
-  if (stride != 1) return 0;
-  return dk_dwconv_fwd_stats_rows(N, H, W, C, 1);
-}
-// The bf16 stride-1 dgrad's rows: it is the bf16 forward launch (dw_dgrad -> launch_dw_fwd with
-// whole output columns per thread), so it writes that launch's rows, not the fp32 dgrad's.
-DK_API int dk_dwconv_dgrad_bf16_stats_rows(int N, int H, int W, int C, int stride) {
-  if (stride != 1) return 0;
-  return dk_dwconv_fwd_bf16_stats_rows(N, H, W, C, 1);
-}
-
-DK_API int dk_dwconv_dgrad_ex_f32(const float* dy, int N, int OH, int OW, int C, const float* w_crs, int R, int S,
-                                  int stride, int pad, float* dx, int H, int W, void* ws, size_t ws_bytes,
-                                  const float* residual, const float* bn_x, const float* bn_mean,
-                                  const float* bn_invstd, const float* bn_gamma, const float* bn_beta, int bn_relu,
-                                  double* part, void* stream) {
-  if ((part != nullptr) != (bn_x != nullptr)) return DK_ERR_ARGS;
-  return dw_dgrad(dy, N, OH, OW, C, w_crs, R, S, stride, pad, dx, H, W, ws, ws_bytes, residual, bn_x,
-                  BnIn{bn_mean, bn_invstd, bn_gamma, bn_beta, bn_relu}, part, as_stream(stream));
-}
-
-DK_API size_t dk_dwconv_wgrad_workspace_bytes(int N, int OH, int OW, int C, int R, int S) {
-  return (size_t)dw_wgrad_blocks(N, OH, OW, C) * C * R * S * sizeof(float);
-}
-
-namespace dk {
+// dw[c][r][s] = sum_{n,oh,ow} dy[n,oh,ow,c] * x[n, oh*st + r - pad, ow*st + s - pad, c] (+ l2 * w)
 template <class T>
 static int dw_wgrad(const T* dy, const T* x, int N, int H, int W, int C, int R, int S, int stride, int pad, int OH,
                     int OW, const float* w_crs, float l2, float* dw_crs, void* ws, size_t ws_bytes,
                     const BnIn& bn, hipStream_t st) {
-  if (C % 4 || !aligned16(x) || !aligned16(dy) || !bn_ok(bn)) return DK_ERR_ARGS;
+  if (C % 4 || !aligned16(x, dy) || !bn_ok(bn)) return DK_ERR_ARGS;
   if (!fits((size_t)N * H * W * C * 4) || !fits((size_t)N * OH * OW * C * 4)) return DK_ERR_ARGS;
-  if (ws_bytes < dk_dwconv_wgrad_workspace_bytes(N, OH, OW, C, R, S)) return DK_ERR_WORKSPACE;
   const int nblk = dw_wgrad_blocks(N, OH, OW, C);
+  if (ws_bytes < (size_t)nblk * C * R * S * sizeof(float)) return DK_ERR_WORKSPACE;
   const int C4 = C / 4;
   const int cgt = C4 < 256 ? C4 : 256;
   const dim3 grid(nblk, cdiv(C4, cgt));
@@ -2005,134 +1954,253 @@ static int dw_wgrad(const T* dy, const T* x, int N, int H, int W, int C, int R, 
   if (rc) return rc;
   return splitk_reduce(part, nblk, 1, C * R * S, dw_crs, w_crs, l2, 0, C, C, 1, 1, st);
 }
-}  // namespace dk
 
-// dw[c][r][s] = sum_{n,oh,ow} dy[n,oh,ow,c] * x[n, oh*st + r - pad, ow*st + s - pad, c] (+ l2 * w)
-DK_API int dk_dwconv_wgrad_f32(const float* dy, const float* x, int N, int H, int W, int C, int R, int S, int stride,
-                               int pad, int OH, int OW, const float* w_crs, float l2, float* dw_crs, void* ws,
-                               size_t ws_bytes, void* stream) {
-  return dw_wgrad(dy, x, N, H, W, C, R, S, stride, pad, OH, OW, w_crs, l2, dw_crs, ws, ws_bytes, BnIn{},
-                  as_stream(stream));
+// dw_bwd_fused_kernel for one (BNX, STATS, RELU1, JOIN) form: columns per thread, with or without
+// the residual's loads.  JM = false (the mask is y > 0: no mask loads) is built for the two-column
+// join form only; the one-column join form tests jn.mask at run time.
+template <bool BNX, bool STATS, bool RELU1, bool JOIN, class T>
+static auto dwb_kernel(int cpt, bool res, bool mask) {
+  if constexpr (JOIN) {
+    if (cpt == 2 && !mask)
+      return res ? dw_bwd_fused_kernel<BNX, STATS, RELU1, JOIN, T, 2, true, false>
+                 : dw_bwd_fused_kernel<BNX, STATS, RELU1, JOIN, T, 2, false, false>;
+  }
+  if (cpt == 2)
+    return res ? dw_bwd_fused_kernel<BNX, STATS, RELU1, JOIN, T, 2, true>
+               : dw_bwd_fused_kernel<BNX, STATS, RELU1, JOIN, T, 2, false>;
+  return res ? dw_bwd_fused_kernel<BNX, STATS, RELU1, JOIN, T, 1, true>
+             : dw_bwd_fused_kernel<BNX, STATS, RELU1, JOIN, T, 1, false>;
 }
 
-// Fused stride-1 backward (dw_bwd_fused_kernel).  Workspace: the weight-gradient partials.
-DK_API int dk_dwconv_bwd_bnbwd_stats_rows(int N, int H, int W, int C) {
-  (void)H;
-  return (C < 4 || C % 4) ? 0 : dwb_strips(N, W, C, dwb_geom(W, C, dwb_cpt(4)));
-}
-// (the join entry dk_dwconv_bwd_bnbwd_join_f32 has the fp32 geometry: these rows)
-
-DK_API size_t dk_dwconv_bwd_bnbwd_workspace_bytes(int N, int H, int W, int C, int R, int S) {
-  return (size_t)dk_dwconv_bwd_bnbwd_stats_rows(N, H, W, C) * C * R * S * sizeof(float);
-}
-
-// bf16 storage: its block geometry may differ (two columns per thread, dwb_geom)
-DK_API int dk_dwconv_bwd_bnbwd_bf16_stats_rows(int N, int H, int W, int C) {
-  (void)H;
-  return (C < 4 || C % 4) ? 0 : dwb_strips(N, W, C, dwb_geom(W, C, dwb_cpt(2), dwb_nt(2)));
-}
-
-DK_API size_t dk_dwconv_bwd_bnbwd_bf16_workspace_bytes(int N, int H, int W, int C, int R, int S) {
-  return (size_t)dk_dwconv_bwd_bnbwd_bf16_stats_rows(N, H, W, C) * C * R * S * sizeof(float);
-}
-
-namespace dk {
+// Fused stride-1 backward (3 x 3, pad 1).  ob: the BatchNorm after the layer; bn: the input
+// BatchNorm applied on load (mean null: none), part its stage-1 partials (dwb_plan's strips rows).
+// jn (fp32, no input BN; dx and part required): the layer's input is a residual join's output and
+// part gets the join BatchNorm's partials instead.  ws: the weight-gradient partials.
 template <class T>
-static int dw_bwd_fused(const T* g, const T* bn_x, int N, int H, int W, int C, const float* out_mean,
-                        const float* out_invstd, const float* out_gamma, const float* out_beta, int out_relu,
-                        const float* k12, const T* x, const float* w_crs, int R, int S, int pad, float l2,
-                        float* dw_crs, T* dx, const T* residual, const float* bn_mean, const float* bn_invstd,
-                        const float* bn_gamma, const float* bn_beta, int bn_relu, double* part, void* ws,
-                        size_t ws_bytes, void* stream) {
-  const hipStream_t st = as_stream(stream);
+static int dw_bwd_fused(const T* g, const T* bn_x, int N, int H, int W, int C, const BnBwdOut& ob, const T* x,
+                        const float* w_crs, int R, int S, int pad, float l2, float* dw_crs, T* dx, const T* residual,
+                        const BnIn& bn, double* part, void* ws, size_t ws_bytes, hipStream_t st,
+                        const JoinBwd* jn = nullptr) {
   if (R != 3 || S != 3 || pad != 1 || C % 4 || N < 1 || H < 1 || W < 1) return DK_ERR_ARGS;
-  const DwbGeom geo = dwb_geom(W, C, dwb_cpt(sizeof(T)), dwb_nt(sizeof(T)));
-  const int cl = geo.cl;
-  if (!g || !bn_x || !x || !w_crs || !dw_crs || !out_mean || !out_invstd || !out_gamma || !out_beta || !k12)
-    return DK_ERR_ARGS;
-  const BnIn bn{bn_mean, bn_invstd, bn_gamma, bn_beta, bn_relu};
-  if (part && !bn_mean) return DK_ERR_ARGS;  // the input BN's partials need the input BN
-  if (!aligned16(g) || !aligned16(bn_x) || !aligned16(x) || (dx && !aligned16(dx)) ||
-      (residual && !aligned16(residual)) || !bn_ok(bn) || !aligned16(out_mean) || !aligned16(out_invstd) ||
-      !aligned16(out_gamma) || !aligned16(out_beta) || !aligned16(k12) || !aligned16(w_crs))
+  if (!all_set(g, bn_x, x, w_crs, dw_crs, ob.mean, ob.invstd, ob.gamma, ob.beta, ob.k12)) return DK_ERR_ARGS;
+  if (jn) {
+    if (sizeof(T) != 4 || bn.mean || !all_set(dx, part, jn->x, jn->mean, jn->invstd) ||
+        !aligned16(jn->x, jn->mean, jn->invstd) || !aligned(4, jn->mask))
+      return DK_ERR_ARGS;
+  } else if (part && !bn.mean) {
+    return DK_ERR_ARGS;  // the input BN's partials need the input BN
+  }
+  if (!aligned16(g, bn_x, x, dx, residual, w_crs, ob.mean, ob.invstd, ob.gamma, ob.beta, ob.k12) || !bn_ok(bn))
     return DK_ERR_ARGS;
   const size_t bytes = (size_t)N * H * W * C * sizeof(T);
   if (!fits(bytes)) return DK_ERR_ARGS;
-  const size_t need = sizeof(T) == 2 ? dk_dwconv_bwd_bnbwd_bf16_workspace_bytes(N, H, W, C, R, S)
-                                      : dk_dwconv_bwd_bnbwd_workspace_bytes(N, H, W, C, R, S);
-  if (ws_bytes < need) return DK_ERR_WORKSPACE;
-  const int strips = dwb_strips(N, W, C, geo);
-  const int nranges = dwb_nranges(N, W, C, geo);
-  const int ncht = (C / 4) / geo.cg;
+  const DwbPlan p = dwb_plan(N, W, C);
+  if (ws_bytes < p.ws_bytes(C, R, S)) return DK_ERR_WORKSPACE;
   float* wpart = static_cast<float*>(ws);
-  const BnBwdOut ob{out_mean, out_invstd, out_gamma, out_beta, k12, out_relu};
-  const dim3 grid((unsigned)(strips * ncht));
-  FoldTail ft;  // an armed in-launch fold of the input BN's partial rows (fold_tail.h)
-  if (!part || !fold_take(part, strips, C, ncht, &ft)) ft.part = nullptr;
-  size_t shm = (size_t)geo.nt * 9 * 4 * sizeof(float);  // the weight-gradient reduction
-  const size_t ring = (size_t)2 * (cl + 2) * geo.cg * sizeof(f32x4);
-  if (ring > shm) shm = ring;
-  // two columns per thread (knob 21)
-  constexpr int CPT2 = 2;
-#define DWB_LAUNCH(BNX_, STATS_, RELU1_)                                                                             \
-  {                                                                                                                  \
-    auto k = geo.cpt == 2 ? (residual ? dw_bwd_fused_kernel<BNX_, STATS_, RELU1_, false, T, CPT2>                 \
-                                      : dw_bwd_fused_kernel<BNX_, STATS_, RELU1_, false, T, CPT2, 256, false>)    \
-                          : (residual ? dw_bwd_fused_kernel<BNX_, STATS_, RELU1_, false, T>                       \
-                                      : dw_bwd_fused_kernel<BNX_, STATS_, RELU1_, false, T, 1, 256, false>);      \
-    if (shm > 65536)                                                                                                 \
-      (void)hipFuncSetAttribute(reinterpret_cast<const void*>(k), hipFuncAttributeMaxDynamicSharedMemorySize,       \
-                                (int)shm);                                                                           \
-    hipLaunchKernelGGL(k, grid, dim3(geo.nt), shm, st, g, bn_x, (uint32_t)bytes, ob, x, bn, w_crs, dx, residual, part,  \
-                       wpart, N, H, W, C, cl, ft, JoinBwd{}, nt_stores(kNtDwBwd), nranges);                                                        \
+  FoldTail ft;  // an armed in-launch fold of the partial rows (fold_tail.h)
+  if (!part || !fold_take(part, p.strips, C, p.ncht, &ft)) ft.part = nullptr;
+#define DWB_KERNEL(BNX_, STATS_, JOIN_)                                                       \
+  (ob.relu ? dwb_kernel<BNX_, STATS_, true, JOIN_, T>(p.geo.cpt, residual, jn && jn->mask)    \
+           : dwb_kernel<BNX_, STATS_, false, JOIN_, T>(p.geo.cpt, residual, jn && jn->mask))
+  auto k = DWB_KERNEL(false, false, false);
+  if (jn) {
+    if constexpr (sizeof(T) == 4) k = DWB_KERNEL(false, false, true);
+  } else if (part) {
+    k = DWB_KERNEL(true, true, false);
+  } else if (bn.mean) {
+    k = DWB_KERNEL(true, false, false);
   }
-  if (out_relu) {
-    if (part) DWB_LAUNCH(true, true, true) else if (bn_mean) DWB_LAUNCH(true, false, true)
-    else DWB_LAUNCH(false, false, true)
-  } else {
-    if (part) DWB_LAUNCH(true, true, false) else if (bn_mean) DWB_LAUNCH(true, false, false)
-    else DWB_LAUNCH(false, false, false)
-  }
-#undef DWB_LAUNCH
+#undef DWB_KERNEL
+  hipLaunchKernelGGL(k, dim3((unsigned)(p.strips * p.ncht)), dim3(256), p.shm, st, g, bn_x, (uint32_t)bytes, ob, x, bn,
+                     w_crs, dx, residual, part, wpart, N, H, W, C, p.geo.cl, ft, jn ? *jn : JoinBwd{},
+                     nt_stores(kNtDwBwd), p.nranges);
   int rc = launch_status();
   if (rc) return rc;
-  return fold_status(wgrad_reduce(wpart, strips, 1, C * R * S, dw_crs, l2 != 0.f ? w_crs : nullptr, l2, st), ft);
+  return fold_status(wgrad_reduce(wpart, p.strips, 1, C * R * S, dw_crs, l2 != 0.f ? w_crs : nullptr, l2, st), ft);
 }
+
+// Fused stride-2 backward (3 x 3, pad 1), as dw_bwd_fused.  jn: the join form (fp32, no input BN;
+// dx and part required; the mask is read off x); residual_lattice = 2: the residual is the compact
+// stride-2 lattice [N][OH][OW][C] (0: dense; the join form only).
+template <class T>
+static int dw_bwd_s2(const T* g, const T* bn_x, int N, int H, int W, int C, int OH, int OW, const BnBwdOut& ob,
+                     const T* x, const float* w_crs, float l2, float* dw_crs, T* dx, const T* residual,
+                     const BnIn& bn, double* part, void* ws, size_t ws_bytes, hipStream_t st,
+                     const JoinBwd* jn = nullptr, int residual_lattice = 0) {
+  if (!dws2_ok(N, H, W, C, OH, OW) || (residual_lattice != 0 && residual_lattice != 2)) return DK_ERR_ARGS;
+  if (!all_set(g, bn_x, x, w_crs, dw_crs, ob.mean, ob.invstd, ob.gamma, ob.beta, ob.k12)) return DK_ERR_ARGS;
+  if (jn) {
+    if (sizeof(T) != 4 || bn.mean || !all_set(dx, part, jn->x, jn->mean, jn->invstd) ||
+        !aligned16(jn->x, jn->mean, jn->invstd))
+      return DK_ERR_ARGS;
+  } else if (part && !bn.mean) {
+    return DK_ERR_ARGS;
+  }
+  // Unlike the stride-1 entry, this one asks of the activations what their 4-channel vector
+  // accesses need (16 bytes in fp32, 8 in bf16; stride 1 asks 16 of both) and nothing of w_crs
+  if (!aligned16(ob.mean, ob.invstd, ob.gamma, ob.beta, ob.k12) || !bn_ok(bn) ||
+      !aligned(4 * sizeof(T), g, bn_x, x, dx, residual))
+    return DK_ERR_ARGS;
+  const size_t xb = (size_t)N * H * W * C * sizeof(T), yb = (size_t)N * OH * OW * C * sizeof(T);
+  if (!fits(xb)) return DK_ERR_ARGS;
+  const int blocks = dws2_blocks(N, H, W, C);
+  if (ws_bytes < dws2_ws_bytes(blocks, C)) return DK_ERR_WORKSPACE;
+  float* wpart = static_cast<float*>(ws);
+  JoinBwd j = jn ? *jn : JoinBwd{};
+  j.res_lat = jn && residual && residual_lattice == 2;
+  FoldTail ft;
+  if (!part || !fold_take(part, blocks, C, 1, &ft)) ft.part = nullptr;
+  const size_t shm = (size_t)256 * 9 * 4 * sizeof(float);
+  // RES = false (the residual's loads and adds compiled out) is built for the forms without a join
+#define DWS2_KERNEL(BNX_, STATS_, JOIN_, RES_)                         \
+  (ob.relu ? dw_bwd_s2_kernel<BNX_, STATS_, true, T, JOIN_, RES_>      \
+           : dw_bwd_s2_kernel<BNX_, STATS_, false, T, JOIN_, RES_>)
+#define DWS2_KERNEL_RES(BNX_, STATS_) \
+  (residual ? DWS2_KERNEL(BNX_, STATS_, false, true) : DWS2_KERNEL(BNX_, STATS_, false, false))
+  auto k = DWS2_KERNEL_RES(false, false);
+  if (jn) {
+    if constexpr (sizeof(T) == 4) k = DWS2_KERNEL(false, false, true, true);
+  } else if (part) {
+    k = DWS2_KERNEL_RES(true, true);
+  } else if (bn.mean) {
+    k = DWS2_KERNEL_RES(true, false);
+  }
+#undef DWS2_KERNEL_RES
+#undef DWS2_KERNEL
+  hipLaunchKernelGGL(k, dim3(blocks), dim3(256), shm, st, g, bn_x, (uint32_t)yb, ob, x, (uint32_t)xb, bn, w_crs, dx,
+                     residual, part, wpart, N, H, W, C, OH, OW, ft, nt_stores(dgrad_nt_fam<T>()), j);
+  int rc = launch_status();
+  if (rc) return rc;
+  return fold_status(wgrad_reduce(wpart, blocks, 1, C * 9, dw_crs, l2 != 0.f ? w_crs : nullptr, l2, st), ft);
+}
+
 }  // namespace dk
 
-DK_API int dk_dwconv_bwd_bnbwd_f32(const float* g, const float* bn_x, int N, int H, int W, int C,
-                                   const float* out_mean, const float* out_invstd, const float* out_gamma,
-                                   const float* out_beta, int out_relu, const float* k12, const float* x,
-                                   const float* w_crs, int R, int S, int pad, float l2, float* dw_crs, float* dx,
-                                   const float* residual, const float* bn_mean, const float* bn_invstd,
-                                   const float* bn_gamma, const float* bn_beta, int bn_relu, double* part,
-                                   void* ws, size_t ws_bytes, void* stream) {
-  return dw_bwd_fused(g, bn_x, N, H, W, C, out_mean, out_invstd, out_gamma, out_beta, out_relu, k12, x, w_crs, R, S,
-                      pad, l2, dw_crs, dx, residual, bn_mean, bn_invstd, bn_gamma, bn_beta, bn_relu, part, ws,
-                      ws_bytes, stream);
+using namespace dk;
+
+// ---------------------------------------------------------------------------------------
+// The C entry points (include/dorknet_hip.h).  bf16 twins: activations / gradients bf16,
+// weights and their gradients fp32, all arithmetic fp32 (the same kernels, T = bf16_t).
+// ---------------------------------------------------------------------------------------
+DK_API int dk_dw_weight_rsc_f32(const float* w_crs, int C, int R, int S, float* w_rsc, void* stream) {
+  const int total = C * R * S;
+  hipLaunchKernelGGL(dw_weight_rsc_kernel, dim3(cdiv(total, 256)), dim3(256), 0, as_stream(stream), w_crs, C, R, S, 0,
+                     w_rsc);
+  return launch_status();
 }
 
-// bf16 storage twin (BASELINE config 5): g, bn_x, x, dx, residual bf16; dy formed in fp32.
-DK_API int dk_dwconv_bwd_bnbwd_bf16(const bf16_t* g, const bf16_t* bn_x, int N, int H, int W, int C,
-                                    const float* out_mean, const float* out_invstd, const float* out_gamma,
-                                    const float* out_beta, int out_relu, const float* k12, const bf16_t* x,
-                                    const float* w_crs, int R, int S, int pad, float l2, float* dw_crs, bf16_t* dx,
-                                    const bf16_t* residual, const float* bn_mean, const float* bn_invstd,
-                                    const float* bn_gamma, const float* bn_beta, int bn_relu, double* part,
-                                    void* ws, size_t ws_bytes, void* stream) {
-  return dw_bwd_fused(g, bn_x, N, H, W, C, out_mean, out_invstd, out_gamma, out_beta, out_relu, k12, x, w_crs, R, S,
-                      pad, l2, dw_crs, dx, residual, bn_mean, bn_invstd, bn_gamma, bn_beta, bn_relu, part, ws,
-                      ws_bytes, stream);
+// ---- forward ----
+DK_API int dk_dwconv_fwd_f32(const float* x, int N, int H, int W, int C, const float* w_rsc, int R, int S, int stride,
+                             int pad, const float* bias, float* y, int OH, int OW, void* stream) {
+  return dw_fwd_dispatch(x, w_rsc, bias, y, N, H, W, C, R, S, stride, OH, OW, pad, BnIn{}, as_stream(stream));
+}
+
+DK_API int dk_dwconv_fwd_bnx_f32(const float* x, int N, int H, int W, int C, const float* w_rsc, int R, int S,
+                                 int stride, int pad, const float* bias, float* y, int OH, int OW,
+                                 const float* bn_mean, const float* bn_invstd, const float* bn_gamma,
+                                 const float* bn_beta, int bn_relu, void* stream) {
+  if (!bn_mean) return DK_ERR_ARGS;
+  return dw_fwd_dispatch(x, w_rsc, bias, y, N, H, W, C, R, S, stride, OH, OW, pad,
+                         BnIn{bn_mean, bn_invstd, bn_gamma, bn_beta, bn_relu}, as_stream(stream));
+}
+
+// Rows of BatchNorm partial statistics dk_dwconv_fwd_ex_f32 writes; 0 = statistics not
+// supported for this channel count (C/4 must divide 256).
+DK_API int dk_dwconv_fwd_stats_rows(int N, int OH, int OW, int C, int stride) {
+  return dw_fwd_rows(N, OH, OW, C, stride, sizeof(float));
+}
+// The bf16 forward's rows (dk_dwconv_fwd_ex_bf16: whole output columns per thread, fewer blocks).
+DK_API int dk_dwconv_fwd_bf16_stats_rows(int N, int OH, int OW, int C, int stride) {
+  return dw_fwd_rows(N, OH, OW, C, stride, sizeof(bf16_t));
+}
+
+// Reads the filters in the reference layout W[C][R][S] (no re-layout copy).
+DK_API int dk_dwconv_fwd_ex_f32(const float* x, int N, int H, int W, int C, const float* w_crs, int R, int S,
+                                int stride, int pad, const float* bias, float* y, int OH, int OW,
+                                const float* bn_mean, const float* bn_invstd, const float* bn_gamma,
+                                const float* bn_beta, int bn_relu, double* stats, void* stream) {
+  if (stride != 1 && stride != 2) return DK_ERR_ARGS;
+  return dw_fwd_dispatch<float>(x, w_crs, bias, y, N, H, W, C, R, S, stride, OH, OW, pad,
+                                BnIn{bn_mean, bn_invstd, bn_gamma, bn_beta, bn_relu}, as_stream(stream), stats,
+                                nullptr, BnIn{}, 1);
+}
+
+DK_API int dk_dwconv_fwd_ex_bf16(const bf16_t* x, int N, int H, int W, int C, const float* w_crs, int R, int S,
+                                 int stride, int pad, const float* bias, bf16_t* y, int OH, int OW,
+                                 const float* bn_mean, const float* bn_invstd, const float* bn_gamma,
+                                 const float* bn_beta, int bn_relu, double* stats, void* stream) {
+  if (stride != 1 && stride != 2) return DK_ERR_ARGS;
+  return dw_fwd_dispatch<bf16_t>(x, w_crs, bias, y, N, H, W, C, R, S, stride, OH, OW, pad,
+                                 BnIn{bn_mean, bn_invstd, bn_gamma, bn_beta, bn_relu}, as_stream(stream), stats,
+                                 nullptr, BnIn{}, 1);
+}
+
+// The layer's input is the residual join y = ReLU(bnA(a) + bnB(b)) (dk_bn_add_f32's operands), formed
+// as the window is loaded and stored once into y_join (+ its ReLU mask, nullable); the rest as
+// dk_dwconv_fwd_ex_f32 without an input BatchNorm.  3 x 3 filters, pad 1, stride 1 or 2.
+DK_API int dk_dwconv_fwd_join_f32(const float* a, const float* a_mean, const float* a_invstd, const float* a_gamma,
+                                  const float* a_beta, int a_relu, const float* b, const float* b_mean,
+                                  const float* b_invstd, const float* b_gamma, const float* b_beta, int b_relu,
+                                  float* y_join, uint8_t* mask, int N, int H, int W, int C, const float* w_crs,
+                                  int stride, const float* bias, float* y, int OH, int OW, double* stats,
+                                  void* stream) {
+  if (stride != 1 && stride != 2) return DK_ERR_ARGS;
+  const JoinFwd jf{b, BnIn{a_mean, a_invstd, a_gamma, a_beta, a_relu}, BnIn{b_mean, b_invstd, b_gamma, b_beta, b_relu},
+                   y_join, mask};
+  if (!all_set(b, y_join) || !aligned16(b, y_join) || !aligned(4, mask) || !bn_ok(jf.ba) || !bn_ok(jf.bb) || C > 512)
+    return DK_ERR_ARGS;
+  return dw_fwd_dispatch<float>(a, w_crs, bias, y, N, H, W, C, 3, 3, stride, OH, OW, 1, BnIn{}, as_stream(stream),
+                                stats, nullptr, BnIn{}, 1, nullptr, &jf);
+}
+
+// ---- input gradient ----
+// w_rsc is the (unflipped) [R][S][C] copy; stride-1 dgrad flips it internally into ws.
+DK_API size_t dk_dwconv_dgrad_workspace_bytes(int C, int R, int S) { return (size_t)C * R * S * sizeof(float); }
+
+DK_API int dk_dwconv_dgrad_f32(const float* dy, int N, int OH, int OW, int C, const float* w_crs, int R, int S,
+                               int stride, int pad, float* dx, int H, int W, void* ws, size_t ws_bytes,
+                               void* stream) {
+  return dw_dgrad<float>(dy, N, OH, OW, C, w_crs, R, S, stride, pad, dx, H, W, ws, ws_bytes, nullptr, nullptr, BnIn{},
+                         nullptr, as_stream(stream));
+}
+
+// Rows of BN-backward partials of the stride-1 dgrad: it is the forward launch (dw_dgrad ->
+// launch_dw_fwd), so bf16 storage writes the bf16 forward's rows, not the fp32 dgrad's.
+DK_API int dk_dwconv_dgrad_stats_rows(int N, int H, int W, int C, int stride) {
+  return stride == 1 ? dw_fwd_rows(N, H, W, C, 1, sizeof(float)) : 0;
+}
+DK_API int dk_dwconv_dgrad_bf16_stats_rows(int N, int H, int W, int C, int stride) {
+  return stride == 1 ? dw_fwd_rows(N, H, W, C, 1, sizeof(bf16_t)) : 0;
+}
+
+DK_API int dk_dwconv_dgrad_ex_f32(const float* dy, int N, int OH, int OW, int C, const float* w_crs, int R, int S,
+                                  int stride, int pad, float* dx, int H, int W, void* ws, size_t ws_bytes,
+                                  const float* residual, const float* bn_x, const float* bn_mean,
+                                  const float* bn_invstd, const float* bn_gamma, const float* bn_beta, int bn_relu,
+                                  double* part, void* stream) {
+  if ((part != nullptr) != (bn_x != nullptr)) return DK_ERR_ARGS;
+  return dw_dgrad(dy, N, OH, OW, C, w_crs, R, S, stride, pad, dx, H, W, ws, ws_bytes, residual, bn_x,
+                  BnIn{bn_mean, bn_invstd, bn_gamma, bn_beta, bn_relu}, part, as_stream(stream));
+}
+
+DK_API int dk_dwconv_dgrad_ex_bf16(const bf16_t* dy, int N, int OH, int OW, int C, const float* w_crs, int R, int S,
+                                   int stride, int pad, bf16_t* dx, int H, int W, void* ws, size_t ws_bytes,
+                                   const bf16_t* residual, const bf16_t* bn_x, const float* bn_mean,
+                                   const float* bn_invstd, const float* bn_gamma, const float* bn_beta, int bn_relu,
+                                   double* part, void* stream) {
+  if ((part != nullptr) != (bn_x != nullptr)) return DK_ERR_ARGS;
+  return dw_dgrad<bf16_t>(dy, N, OH, OW, C, w_crs, R, S, stride, pad, dx, H, W, ws, ws_bytes, residual, bn_x,
+                          BnIn{bn_mean, bn_invstd, bn_gamma, bn_beta, bn_relu}, part, as_stream(stream));
 }
 
 // Rows of join partials dk_dwconv_dgrad_join_f32 writes (0: the geometry has no join variant).
 DK_API int dk_dwconv_dgrad_join_rows(int N, int H, int W, int C, int R, int S, int stride, int pad) {
-  if (C % 4 || C / 4 > 256 || 256 % (C / 4)) return 0;
-  const bool ok = (R == 3 && S == 3 && stride == 2 && pad == 1) || (R == 5 && S == 5 && stride == 2 && pad == 2) ||
-                  (R == 1 && S == 1 && stride == 2 && pad == 0);
-  if (!ok) return 0;
-  const long long items = (long long)N * cdiv(H, stride) * cdiv(cdiv(W, stride), 4) * (C / 4);
-  return (int)cdivll(items, 256);
+  if (!dw_rows_ok(C)) return 0;
+#define DW_SUBPIX_ROWS(RR, SS, STR, PD) \
+  if (R == RR && S == SS && stride == STR && pad == PD) return (int)dw_subpix_blocks(N, H, W, C, STR);
+  DW_SUBPIX_CASES(DW_SUBPIX_ROWS)
+#undef DW_SUBPIX_ROWS
+  return 0;
 }
 
 // Strided (sub-pixel) input gradient whose input is a residual join's output: dx = (dgrad +
@@ -2145,168 +2213,79 @@ DK_API int dk_dwconv_dgrad_join_f32(const float* dy, int N, int OH, int OW, int 
                                     const float* join_x, const float* join_mean, const float* join_invstd,
                                     double* part, void* stream) {
   if (residual_lattice != 0 && residual_lattice != stride) return DK_ERR_ARGS;
-  if (!join_mask || !join_x || !join_mean || !join_invstd || !part ||
+  if (!all_set(join_mask, join_x, join_mean, join_invstd, part) ||
       dk_dwconv_dgrad_join_rows(N, H, W, C, R, S, stride, pad) == 0)
     return DK_ERR_ARGS;
-  if (!aligned16(join_x) || !aligned16(join_mean) || !aligned16(join_invstd) ||
-      (reinterpret_cast<uintptr_t>(join_mask) & 3))
-    return DK_ERR_ARGS;
+  if (!aligned16(join_x, join_mean, join_invstd) || !aligned(4, join_mask)) return DK_ERR_ARGS;
   const JoinBwd jn{join_mask, join_x, join_mean, join_invstd, residual_lattice ? 1 : 0};
   return dw_dgrad<float>(dy, N, OH, OW, C, w_crs, R, S, stride, pad, dx, H, W, ws, ws_bytes, residual, nullptr,
                          BnIn{}, part, as_stream(stream), &jn);
 }
 
-// ---- fused stride-2 depthwise backward (dw_bwd_s2_kernel) ----
-namespace dk {
-static int dws2_blocks(int N, int H, int W, int C) {
-  const int C4 = C / 4, IPB = 256 / C4;
-  const long long items = (long long)N * ((H + 1) / 2) * ((((W + 1) / 2) + 1) / 2);
-  long long b = (items + IPB - 1) / IPB;
-  const int target = knob(kKnobDwbBlocks) * 2 / 3;  // two resident blocks per CU
-  if (target > 0 && b > target) b = target;
-  return b < 1 ? 1 : (int)b;
-}
-static bool dws2_ok(int N, int H, int W, int C, int OH, int OW) {
-  return N >= 1 && H >= 1 && W >= 1 && C >= 4 && C % 4 == 0 && 256 % (C / 4) == 0 && OH == (H + 1) / 2 &&
-         OW == (W + 1) / 2;
-}
-}  // namespace dk
-
-DK_API int dk_dwconv_bwd_s2_stats_rows(int N, int H, int W, int C) {
-  return dk::dws2_ok(N, H, W, C, (H + 1) / 2, (W + 1) / 2) ? dk::dws2_blocks(N, H, W, C) : 0;
+// ---- weight gradient ----
+DK_API size_t dk_dwconv_wgrad_workspace_bytes(int N, int OH, int OW, int C, int R, int S) {
+  return (size_t)dw_wgrad_blocks(N, OH, OW, C) * C * R * S * sizeof(float);
 }
 
-DK_API size_t dk_dwconv_bwd_s2_workspace_bytes(int N, int H, int W, int C) {
-  return (size_t)dk_dwconv_bwd_s2_stats_rows(N, H, W, C) * C * 9 * sizeof(float);
+DK_API int dk_dwconv_wgrad_f32(const float* dy, const float* x, int N, int H, int W, int C, int R, int S, int stride,
+                               int pad, int OH, int OW, const float* w_crs, float l2, float* dw_crs, void* ws,
+                               size_t ws_bytes, void* stream) {
+  return dw_wgrad(dy, x, N, H, W, C, R, S, stride, pad, OH, OW, w_crs, l2, dw_crs, ws, ws_bytes, BnIn{},
+                  as_stream(stream));
 }
 
-namespace dk {
-template <class T>
-static int dw_bwd_s2(const T* g, const T* bn_x, int N, int H, int W, int C, int OH, int OW, const float* out_mean,
-                     const float* out_invstd, const float* out_gamma, const float* out_beta, int out_relu,
-                     const float* k12, const T* x, const float* w_crs, float l2, float* dw_crs, T* dx,
-                     const T* residual, const float* bn_mean, const float* bn_invstd, const float* bn_gamma,
-                     const float* bn_beta, int bn_relu, double* part, void* ws, size_t ws_bytes, void* stream) {
-  const hipStream_t st = as_stream(stream);
-  if (!dws2_ok(N, H, W, C, OH, OW)) return DK_ERR_ARGS;
-  if (!g || !bn_x || !x || !w_crs || !dw_crs || !out_mean || !out_invstd || !out_gamma || !out_beta || !k12)
-    return DK_ERR_ARGS;
-  const BnIn bn{bn_mean, bn_invstd, bn_gamma, bn_beta, bn_relu};
-  if (part && !bn_mean) return DK_ERR_ARGS;
-  if (!aligned16(out_mean) || !aligned16(out_invstd) || !aligned16(out_gamma) || !aligned16(out_beta) ||
-      !aligned16(k12) || !bn_ok(bn) ||
-      ((reinterpret_cast<uintptr_t>(g) | reinterpret_cast<uintptr_t>(bn_x) | reinterpret_cast<uintptr_t>(x) |
-        reinterpret_cast<uintptr_t>(dx) | reinterpret_cast<uintptr_t>(residual)) & (4 * sizeof(T) - 1)))
-    return DK_ERR_ARGS;  // (dx and the residual take 4-channel vector stores / loads too; null passes)
-  const size_t xb = (size_t)N * H * W * C * sizeof(T), yb = (size_t)N * OH * OW * C * sizeof(T);
-  if (!fits(xb)) return DK_ERR_ARGS;
-  if (ws_bytes < dk_dwconv_bwd_s2_workspace_bytes(N, H, W, C)) return DK_ERR_WORKSPACE;
-  const int blocks = dws2_blocks(N, H, W, C);
-  float* wpart = static_cast<float*>(ws);
-  const BnBwdOut ob{out_mean, out_invstd, out_gamma, out_beta, k12, out_relu};
-  FoldTail ft;
-  if (!part || !fold_take(part, blocks, C, 1, &ft)) ft.part = nullptr;
-  const size_t shm = (size_t)256 * 9 * 4 * sizeof(float);
-#define DWS2_LAUNCH(BNX_, STATS_, RELU1_)                                                                           \
-  do {                                                                                                              \
-    if (residual)                                                                                                   \
-      hipLaunchKernelGGL((dw_bwd_s2_kernel<BNX_, STATS_, RELU1_, T>), dim3(blocks), dim3(256), shm, st, g, bn_x,   \
-                         (uint32_t)yb, ob, x, (uint32_t)xb, bn, w_crs, dx, residual, part, wpart, N, H, W, C, OH, OW, \
-                         ft, nt_stores(dgrad_nt_fam<T>()));                                                                \
-    else                                                                                                            \
-      hipLaunchKernelGGL((dw_bwd_s2_kernel<BNX_, STATS_, RELU1_, T, false, false>), dim3(blocks), dim3(256), shm,  \
-                         st, g, bn_x, (uint32_t)yb, ob, x, (uint32_t)xb, bn, w_crs, dx, residual, part, wpart, N, H, \
-                         W, C, OH, OW, ft, nt_stores(dgrad_nt_fam<T>()));                                                  \
-  } while (0)
-  if (out_relu) {
-    if (part) DWS2_LAUNCH(true, true, true); else if (bn_mean) DWS2_LAUNCH(true, false, true);
-    else DWS2_LAUNCH(false, false, true);
-  } else {
-    if (part) DWS2_LAUNCH(true, true, false); else if (bn_mean) DWS2_LAUNCH(true, false, false);
-    else DWS2_LAUNCH(false, false, false);
-  }
-#undef DWS2_LAUNCH
-  int rc = launch_status();
-  if (rc) return rc;
-  return fold_status(wgrad_reduce(wpart, blocks, 1, C * 9, dw_crs, l2 != 0.f ? w_crs : nullptr, l2, st), ft);
-}
-}  // namespace dk
-
-// Fused stride-2 depthwise backward (3x3, pad 1): as dk_dwconv_bwd_bnbwd_f32 for a stride-2 layer.
-// g / bn_x: the following BatchNorm's output gradient and raw input (N x OH x OW x C); x: this
-// layer's input (N x H x W x C) with the input BN bn_* applied on load (bn_mean NULL: none); dx
-// (NULL: weight gradient only) gets dgrad (+ residual); part: the input BN's stage-1 partials,
-// dk_dwconv_bwd_s2_stats_rows rows.  OH = ceil(H / 2), OW = ceil(W / 2); C / 4 divides 256.
-DK_API int dk_dwconv_bwd_s2_bnbwd_f32(const float* g, const float* bn_x, int N, int H, int W, int C, int OH, int OW,
-                                      const float* out_mean, const float* out_invstd, const float* out_gamma,
-                                      const float* out_beta, int out_relu, const float* k12, const float* x,
-                                      const float* w_crs, float l2, float* dw_crs, float* dx, const float* residual,
-                                      const float* bn_mean, const float* bn_invstd, const float* bn_gamma,
-                                      const float* bn_beta, int bn_relu, double* part, void* ws, size_t ws_bytes,
-                                      void* stream) {
-  return dk::dw_bwd_s2(g, bn_x, N, H, W, C, OH, OW, out_mean, out_invstd, out_gamma, out_beta, out_relu, k12, x,
-                       w_crs, l2, dw_crs, dx, residual, bn_mean, bn_invstd, bn_gamma, bn_beta, bn_relu, part, ws,
-                       ws_bytes, stream);
+DK_API int dk_dwconv_wgrad_bnx_f32(const float* dy, const float* x, int N, int H, int W, int C, int R, int S,
+                                   int stride, int pad, int OH, int OW, const float* w_crs, float l2, float* dw_crs,
+                                   void* ws, size_t ws_bytes, const float* bn_mean, const float* bn_invstd,
+                                   const float* bn_gamma, const float* bn_beta, int bn_relu, void* stream) {
+  if (!bn_mean) return DK_ERR_ARGS;
+  return dw_wgrad(dy, x, N, H, W, C, R, S, stride, pad, OH, OW, w_crs, l2, dw_crs, ws, ws_bytes,
+                  BnIn{bn_mean, bn_invstd, bn_gamma, bn_beta, bn_relu}, as_stream(stream));
 }
 
-// The join form (fp32): x is a residual block's output y = ReLU(bn_j(join_x) + skip), no input BN;
-// dx = (dgrad + residual) * (y > 0) and part (dk_dwconv_bwd_s2_stats_rows x 2 x C, required) gets
-// stage 1 of bn_j's backward (dk_dwconv_dgrad_join_f32's work on the stride-2 path).
-// residual_lattice = 2: the residual is the compact stride-2 lattice [N][OH][OW][C] (0: dense).
-DK_API int dk_dwconv_bwd_s2_bnbwd_join_f32(const float* g, const float* bn_x, int N, int H, int W, int C, int OH,
-                                           int OW, const float* out_mean, const float* out_invstd,
-                                           const float* out_gamma, const float* out_beta, int out_relu,
-                                           const float* k12, const float* x, const float* w_crs, float l2,
-                                           float* dw_crs, float* dx, const float* residual, int residual_lattice,
-                                           const float* join_x, const float* join_mean, const float* join_invstd,
-                                           double* part, void* ws, size_t ws_bytes, void* stream) {
-  using namespace dk;
-  const hipStream_t st = as_stream(stream);
-  if (!dws2_ok(N, H, W, C, OH, OW) || (residual_lattice != 0 && residual_lattice != 2)) return DK_ERR_ARGS;
-  if (!g || !bn_x || !x || !w_crs || !dw_crs || !dx || !out_mean || !out_invstd || !out_gamma || !out_beta || !k12 ||
-      !join_x || !join_mean || !join_invstd || !part)
-    return DK_ERR_ARGS;
-  if (!aligned16(out_mean) || !aligned16(out_invstd) || !aligned16(out_gamma) || !aligned16(out_beta) ||
-      !aligned16(k12) || !aligned16(g) || !aligned16(bn_x) || !aligned16(x) || !aligned16(dx) ||
-      !aligned16(join_x) || !aligned16(join_mean) || !aligned16(join_invstd) || (residual && !aligned16(residual)))
-    return DK_ERR_ARGS;
-  const size_t xb = (size_t)N * H * W * C * sizeof(float), yb = (size_t)N * OH * OW * C * sizeof(float);
-  if (!fits(xb)) return DK_ERR_ARGS;
-  if (ws_bytes < dk_dwconv_bwd_s2_workspace_bytes(N, H, W, C)) return DK_ERR_WORKSPACE;
-  const int blocks = dws2_blocks(N, H, W, C);
-  float* wpart = static_cast<float*>(ws);
-  const BnBwdOut ob{out_mean, out_invstd, out_gamma, out_beta, k12, out_relu};
-  JoinBwd jn{};
-  jn.x = join_x;
-  jn.mean = join_mean;
-  jn.invstd = join_invstd;
-  jn.res_lat = residual && residual_lattice == 2;
-  FoldTail ft;
-  if (!fold_take(part, blocks, C, 1, &ft)) ft.part = nullptr;
-  const size_t shm = (size_t)256 * 9 * 4 * sizeof(float);
-  if (out_relu)
-    hipLaunchKernelGGL((dw_bwd_s2_kernel<false, false, true, float, true>), dim3(blocks), dim3(256), shm, st, g, bn_x,
-                       (uint32_t)yb, ob, x, (uint32_t)xb, BnIn{}, w_crs, dx, residual, part, wpart, N, H, W, C, OH, OW,
-                       ft, nt_stores(kNtDwDgrad), jn);
-  else
-    hipLaunchKernelGGL((dw_bwd_s2_kernel<false, false, false, float, true>), dim3(blocks), dim3(256), shm, st, g,
-                       bn_x, (uint32_t)yb, ob, x, (uint32_t)xb, BnIn{}, w_crs, dx, residual, part, wpart, N, H, W, C,
-                       OH, OW, ft, nt_stores(kNtDwDgrad), jn);
-  int rc = launch_status();
-  if (rc) return rc;
-  return fold_status(wgrad_reduce(wpart, blocks, 1, C * 9, dw_crs, l2 != 0.f ? w_crs : nullptr, l2, st), ft);
+DK_API int dk_dwconv_wgrad_bnx_bf16(const bf16_t* dy, const bf16_t* x, int N, int H, int W, int C, int R, int S,
+                                    int stride, int pad, int OH, int OW, const float* w_crs, float l2, float* dw_crs,
+                                    void* ws, size_t ws_bytes, const float* bn_mean, const float* bn_invstd,
+                                    const float* bn_gamma, const float* bn_beta, int bn_relu, void* stream) {
+  return dw_wgrad<bf16_t>(dy, x, N, H, W, C, R, S, stride, pad, OH, OW, w_crs, l2, dw_crs, ws, ws_bytes,
+                          BnIn{bn_mean, bn_invstd, bn_gamma, bn_beta, bn_relu}, as_stream(stream));
 }
 
-DK_API int dk_dwconv_bwd_s2_bnbwd_bf16(const bf16_t* g, const bf16_t* bn_x, int N, int H, int W, int C, int OH,
-                                       int OW, const float* out_mean, const float* out_invstd, const float* out_gamma,
-                                       const float* out_beta, int out_relu, const float* k12, const bf16_t* x,
-                                       const float* w_crs, float l2, float* dw_crs, bf16_t* dx,
-                                       const bf16_t* residual, const float* bn_mean, const float* bn_invstd,
-                                       const float* bn_gamma, const float* bn_beta, int bn_relu, double* part,
-                                       void* ws, size_t ws_bytes, void* stream) {
-  return dk::dw_bwd_s2(g, bn_x, N, H, W, C, OH, OW, out_mean, out_invstd, out_gamma, out_beta, out_relu, k12, x,
-                       w_crs, l2, dw_crs, dx, residual, bn_mean, bn_invstd, bn_gamma, bn_beta, bn_relu, part, ws,
-                       ws_bytes, stream);
+// ---- fused stride-1 backward (dw_bwd_fused_kernel).  Workspace: the weight-gradient partials. ----
+// The rows and workspace are those of dwb_plan for fp32 and bf16 alike (the join entry too); the
+// bf16 queries are separate names because its block geometry may differ.
+DK_API int dk_dwconv_bwd_bnbwd_stats_rows(int N, int, int W, int C) { return dwb_rows(N, W, C); }
+DK_API int dk_dwconv_bwd_bnbwd_bf16_stats_rows(int N, int, int W, int C) { return dwb_rows(N, W, C); }
+DK_API size_t dk_dwconv_bwd_bnbwd_workspace_bytes(int N, int, int W, int C, int R, int S) {
+  return dwb_ws_bytes(N, W, C, R, S);
+}
+DK_API size_t dk_dwconv_bwd_bnbwd_bf16_workspace_bytes(int N, int, int W, int C, int R, int S) {
+  return dwb_ws_bytes(N, W, C, R, S);
+}
+
+DK_API int dk_dwconv_bwd_bnbwd_f32(const float* g, const float* bn_x, int N, int H, int W, int C,
+                                   const float* out_mean, const float* out_invstd, const float* out_gamma,
+                                   const float* out_beta, int out_relu, const float* k12, const float* x,
+                                   const float* w_crs, int R, int S, int pad, float l2, float* dw_crs, float* dx,
+                                   const float* residual, const float* bn_mean, const float* bn_invstd,
+                                   const float* bn_gamma, const float* bn_beta, int bn_relu, double* part,
+                                   void* ws, size_t ws_bytes, void* stream) {
+  return dw_bwd_fused(g, bn_x, N, H, W, C, BnBwdOut{out_mean, out_invstd, out_gamma, out_beta, k12, out_relu}, x,
+                      w_crs, R, S, pad, l2, dw_crs, dx, residual, BnIn{bn_mean, bn_invstd, bn_gamma, bn_beta, bn_relu},
+                      part, ws, ws_bytes, as_stream(stream));
+}
+
+// bf16 storage twin (BASELINE config 5): g, bn_x, x, dx, residual bf16; dy formed in fp32.
+DK_API int dk_dwconv_bwd_bnbwd_bf16(const bf16_t* g, const bf16_t* bn_x, int N, int H, int W, int C,
+                                    const float* out_mean, const float* out_invstd, const float* out_gamma,
+                                    const float* out_beta, int out_relu, const float* k12, const bf16_t* x,
+                                    const float* w_crs, int R, int S, int pad, float l2, float* dw_crs, bf16_t* dx,
+                                    const bf16_t* residual, const float* bn_mean, const float* bn_invstd,
+                                    const float* bn_gamma, const float* bn_beta, int bn_relu, double* part,
+                                    void* ws, size_t ws_bytes, void* stream) {
+  return dw_bwd_fused(g, bn_x, N, H, W, C, BnBwdOut{out_mean, out_invstd, out_gamma, out_beta, k12, out_relu}, x,
+                      w_crs, R, S, pad, l2, dw_crs, dx, residual, BnIn{bn_mean, bn_invstd, bn_gamma, bn_beta, bn_relu},
+                      part, ws, ws_bytes, as_stream(stream));
 }
 
 // dk_dwconv_bwd_bnbwd_f32 for a layer whose input is a residual join's output (no input BN): dx
@@ -2321,95 +2300,60 @@ DK_API int dk_dwconv_bwd_bnbwd_join_f32(const float* g, const float* bn_x, int N
                                         const float* residual, const uint8_t* join_mask, const float* join_x,
                                         const float* join_mean, const float* join_invstd, double* part, void* ws,
                                         size_t ws_bytes, void* stream) {
-  const hipStream_t st = as_stream(stream);
-  if (R != 3 || S != 3 || pad != 1 || C % 4 || N < 1 || H < 1 || W < 1) return DK_ERR_ARGS;
-  const DwbGeom geo = dwb_geom(W, C, dwb_cpt(4));
-  const int cl = geo.cl;
-  if (!g || !bn_x || !x || !w_crs || !dw_crs || !dx || !out_mean || !out_invstd || !out_gamma || !out_beta ||
-      !k12 || !join_x || !join_mean || !join_invstd || !part)
-    return DK_ERR_ARGS;
-  if (!aligned16(g) || !aligned16(bn_x) || !aligned16(x) || !aligned16(dx) || (residual && !aligned16(residual)) ||
-      !aligned16(out_mean) || !aligned16(out_invstd) || !aligned16(out_gamma) || !aligned16(out_beta) ||
-      !aligned16(k12) || !aligned16(w_crs) || !aligned16(join_x) || !aligned16(join_mean) ||
-      !aligned16(join_invstd) || (reinterpret_cast<uintptr_t>(join_mask) & 3))
-    return DK_ERR_ARGS;
-  const size_t bytes = (size_t)N * H * W * C * sizeof(float);
-  if (!fits(bytes)) return DK_ERR_ARGS;
-  if (ws_bytes < dk_dwconv_bwd_bnbwd_workspace_bytes(N, H, W, C, R, S)) return DK_ERR_WORKSPACE;
-  const int strips = dwb_strips(N, W, C, geo);
-  const int nranges = dwb_nranges(N, W, C, geo);
-  const int ncht = (C / 4) / geo.cg;
-  float* wpart = static_cast<float*>(ws);
-  const BnBwdOut ob{out_mean, out_invstd, out_gamma, out_beta, k12, out_relu};
   const JoinBwd jn{join_mask, join_x, join_mean, join_invstd};
-  const dim3 grid((unsigned)(strips * ncht));
-  FoldTail ft;  // an armed in-launch fold of the join BN's partial rows (fold_tail.h)
-  if (!fold_take(part, strips, C, ncht, &ft)) ft.part = nullptr;
-  size_t shm = (size_t)256 * 9 * 4 * sizeof(float);
-  const size_t ring = (size_t)2 * (cl + 2) * geo.cg * sizeof(f32x4);
-  if (ring > shm) shm = ring;
-#define DWJ_LAUNCH(RELU1_)                                                                                           \
-  {                                                                                                                  \
-    auto k = geo.cpt == 2                                                                                          \
-                 ? (join_mask ? (residual ? dw_bwd_fused_kernel<false, false, RELU1_, true, float, 2>                \
-                                          : dw_bwd_fused_kernel<false, false, RELU1_, true, float, 2, 256, false>)   \
-                              : (residual ? dw_bwd_fused_kernel<false, false, RELU1_, true, float, 2, 256, true, false> \
-                                          : dw_bwd_fused_kernel<false, false, RELU1_, true, float, 2, 256, false, false>)) \
-                 : (residual ? dw_bwd_fused_kernel<false, false, RELU1_, true>                                        \
-                             : dw_bwd_fused_kernel<false, false, RELU1_, true, float, 1, 256, false>);               \
-    if (shm > 65536)                                                                                                 \
-      (void)hipFuncSetAttribute(reinterpret_cast<const void*>(k), hipFuncAttributeMaxDynamicSharedMemorySize,       \
-                                (int)shm);                                                                           \
-    hipLaunchKernelGGL(k, grid, dim3(256), shm, st, g, bn_x, (uint32_t)bytes, ob, x, BnIn{}, w_crs, dx, residual,    \
-                       part, wpart, N, H, W, C, cl, ft, jn, nt_stores(kNtDwBwd), nranges);                                                         \
-  }
-  if (out_relu)
-    DWJ_LAUNCH(true)
-  else
-    DWJ_LAUNCH(false)
-#undef DWJ_LAUNCH
-  int rc = launch_status();
-  if (rc) return rc;
-  return fold_status(wgrad_reduce(wpart, strips, 1, C * R * S, dw_crs, l2 != 0.f ? w_crs : nullptr, l2, st), ft);
+  return dw_bwd_fused(g, bn_x, N, H, W, C, BnBwdOut{out_mean, out_invstd, out_gamma, out_beta, k12, out_relu}, x,
+                      w_crs, R, S, pad, l2, dw_crs, dx, residual, BnIn{}, part, ws, ws_bytes, as_stream(stream), &jn);
 }
 
-DK_API int dk_dwconv_wgrad_bnx_f32(const float* dy, const float* x, int N, int H, int W, int C, int R, int S,
-                                   int stride, int pad, int OH, int OW, const float* w_crs, float l2, float* dw_crs,
-                                   void* ws, size_t ws_bytes, const float* bn_mean, const float* bn_invstd,
-                                   const float* bn_gamma, const float* bn_beta, int bn_relu, void* stream) {
-  if (!bn_mean) return DK_ERR_ARGS;
-  return dw_wgrad(dy, x, N, H, W, C, R, S, stride, pad, OH, OW, w_crs, l2, dw_crs, ws, ws_bytes,
-                  BnIn{bn_mean, bn_invstd, bn_gamma, bn_beta, bn_relu}, as_stream(stream));
+// ---- fused stride-2 backward (dw_bwd_s2_kernel) ----
+DK_API int dk_dwconv_bwd_s2_stats_rows(int N, int H, int W, int C) { return dws2_rows(N, H, W, C); }
+
+DK_API size_t dk_dwconv_bwd_s2_workspace_bytes(int N, int H, int W, int C) {
+  return dws2_ws_bytes(dws2_rows(N, H, W, C), C);
 }
 
-// ---------------------------------------------------------------------------------------
-// bf16 storage (BASELINE config 5): activations / gradients bf16, weights and their
-// gradients fp32, all arithmetic fp32 (same kernels, T = bf16_t).
-// ---------------------------------------------------------------------------------------
-DK_API int dk_dwconv_fwd_ex_bf16(const bf16_t* x, int N, int H, int W, int C, const float* w_crs, int R, int S,
-                                 int stride, int pad, const float* bias, bf16_t* y, int OH, int OW,
-                                 const float* bn_mean, const float* bn_invstd, const float* bn_gamma,
-                                 const float* bn_beta, int bn_relu, double* stats, void* stream) {
-  if (stride != 1 && stride != 2) return DK_ERR_ARGS;
-  return dw_fwd_dispatch<bf16_t>(x, w_crs, bias, y, N, H, W, C, R, S, stride, OH, OW, pad,
-                                 BnIn{bn_mean, bn_invstd, bn_gamma, bn_beta, bn_relu}, as_stream(stream), stats,
-                                 nullptr, BnIn{}, 1);
+// Fused stride-2 depthwise backward (3x3, pad 1): as dk_dwconv_bwd_bnbwd_f32 for a stride-2 layer.
+// g / bn_x: the following BatchNorm's output gradient and raw input (N x OH x OW x C); x: this
+// layer's input (N x H x W x C) with the input BN bn_* applied on load (bn_mean NULL: none); dx
+// (NULL: weight gradient only) gets dgrad (+ residual); part: the input BN's stage-1 partials,
+// dk_dwconv_bwd_s2_stats_rows rows.  OH = ceil(H / 2), OW = ceil(W / 2); C / 4 divides 256.
+DK_API int dk_dwconv_bwd_s2_bnbwd_f32(const float* g, const float* bn_x, int N, int H, int W, int C, int OH, int OW,
+                                      const float* out_mean, const float* out_invstd, const float* out_gamma,
+                                      const float* out_beta, int out_relu, const float* k12, const float* x,
+                                      const float* w_crs, float l2, float* dw_crs, float* dx, const float* residual,
+                                      const float* bn_mean, const float* bn_invstd, const float* bn_gamma,
+                                      const float* bn_beta, int bn_relu, double* part, void* ws, size_t ws_bytes,
+                                      void* stream) {
+  return dw_bwd_s2(g, bn_x, N, H, W, C, OH, OW, BnBwdOut{out_mean, out_invstd, out_gamma, out_beta, k12, out_relu}, x,
+                   w_crs, l2, dw_crs, dx, residual, BnIn{bn_mean, bn_invstd, bn_gamma, bn_beta, bn_relu}, part, ws,
+                   ws_bytes, as_stream(stream));
 }
 
-DK_API int dk_dwconv_dgrad_ex_bf16(const bf16_t* dy, int N, int OH, int OW, int C, const float* w_crs, int R, int S,
-                                   int stride, int pad, bf16_t* dx, int H, int W, void* ws, size_t ws_bytes,
-                                   const bf16_t* residual, const bf16_t* bn_x, const float* bn_mean,
-                                   const float* bn_invstd, const float* bn_gamma, const float* bn_beta, int bn_relu,
-                                   double* part, void* stream) {
-  if ((part != nullptr) != (bn_x != nullptr)) return DK_ERR_ARGS;
-  return dw_dgrad<bf16_t>(dy, N, OH, OW, C, w_crs, R, S, stride, pad, dx, H, W, ws, ws_bytes, residual, bn_x,
-                          BnIn{bn_mean, bn_invstd, bn_gamma, bn_beta, bn_relu}, part, as_stream(stream));
+DK_API int dk_dwconv_bwd_s2_bnbwd_bf16(const bf16_t* g, const bf16_t* bn_x, int N, int H, int W, int C, int OH,
+                                       int OW, const float* out_mean, const float* out_invstd, const float* out_gamma,
+                                       const float* out_beta, int out_relu, const float* k12, const bf16_t* x,
+                                       const float* w_crs, float l2, float* dw_crs, bf16_t* dx,
+                                       const bf16_t* residual, const float* bn_mean, const float* bn_invstd,
+                                       const float* bn_gamma, const float* bn_beta, int bn_relu, double* part,
+                                       void* ws, size_t ws_bytes, void* stream) {
+  return dw_bwd_s2(g, bn_x, N, H, W, C, OH, OW, BnBwdOut{out_mean, out_invstd, out_gamma, out_beta, k12, out_relu}, x,
+                   w_crs, l2, dw_crs, dx, residual, BnIn{bn_mean, bn_invstd, bn_gamma, bn_beta, bn_relu}, part, ws,
+                   ws_bytes, as_stream(stream));
 }
 
-DK_API int dk_dwconv_wgrad_bnx_bf16(const bf16_t* dy, const bf16_t* x, int N, int H, int W, int C, int R, int S,
-                                    int stride, int pad, int OH, int OW, const float* w_crs, float l2, float* dw_crs,
-                                    void* ws, size_t ws_bytes, const float* bn_mean, const float* bn_invstd,
-                                    const float* bn_gamma, const float* bn_beta, int bn_relu, void* stream) {
-  return dw_wgrad<bf16_t>(dy, x, N, H, W, C, R, S, stride, pad, OH, OW, w_crs, l2, dw_crs, ws, ws_bytes,
-                          BnIn{bn_mean, bn_invstd, bn_gamma, bn_beta, bn_relu}, as_stream(stream));
+// The join form (fp32): x is a residual block's output y = ReLU(bn_j(join_x) + skip), no input BN;
+// dx = (dgrad + residual) * (y > 0) and part (dk_dwconv_bwd_s2_stats_rows x 2 x C, required) gets
+// stage 1 of bn_j's backward (dk_dwconv_dgrad_join_f32's work on the stride-2 path).
+// residual_lattice = 2: the residual is the compact stride-2 lattice [N][OH][OW][C] (0: dense).
+DK_API int dk_dwconv_bwd_s2_bnbwd_join_f32(const float* g, const float* bn_x, int N, int H, int W, int C, int OH,
+                                           int OW, const float* out_mean, const float* out_invstd,
+                                           const float* out_gamma, const float* out_beta, int out_relu,
+                                           const float* k12, const float* x, const float* w_crs, float l2,
+                                           float* dw_crs, float* dx, const float* residual, int residual_lattice,
+                                           const float* join_x, const float* join_mean, const float* join_invstd,
+                                           double* part, void* ws, size_t ws_bytes, void* stream) {
+  const JoinBwd jn{nullptr, join_x, join_mean, join_invstd};
+  return dw_bwd_s2(g, bn_x, N, H, W, C, OH, OW, BnBwdOut{out_mean, out_invstd, out_gamma, out_beta, k12, out_relu}, x,
+                   w_crs, l2, dw_crs, dx, residual, BnIn{}, part, ws, ws_bytes, as_stream(stream), &jn,
+                   residual_lattice);
 }

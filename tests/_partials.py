@@ -487,13 +487,13 @@ def relu_bwd_partial(N, C, H, W):
 
 # Longest chain a kernel accumulates in fp32 before it widens to fp64, with the line it is read
 # from (k = 1: every term is widened on its own).
-K_DW_FWD = (1, "depthwise.hip:437-439, each stored y widened before the add")
-K_DW_FWD16 = (4, "depthwise.hip:431-433 and :456-457, a thread's row of TW <= 4 stored values in fp32, then fp64")
-K_DW_DGRAD = (1, "depthwise.hip:447-448, g and g * x_hat widened per element")
-K_DW_SUBPIX = (1, "depthwise.hip:649-650 / :658-659")
-K_DW_BWD = (1, "depthwise.hip:1216-1217")
-K_DW_BWD_JOIN = (1, "depthwise.hip:1196-1197")
-K_DW_BWD_S2 = (1, "depthwise.hip:1577-1578 / :1589-1590")
+K_DW_FWD = (1, "depthwise.hip:439-441, each stored y widened before the add")
+K_DW_FWD16 = (4, "depthwise.hip:433-435 and :458-459, a thread's row of TW <= 4 stored values in fp32, then fp64")
+K_DW_DGRAD = (1, "depthwise.hip:449-450, g and g * x_hat widened per element")
+K_DW_SUBPIX = (1, "depthwise.hip:651-652 / :660-661")
+K_DW_BWD = (1, "depthwise.hip:1219-1220")
+K_DW_BWD_JOIN = (1, "depthwise.hip:1199-1200")
+K_DW_BWD_S2 = (1, "depthwise.hip:1580-1581 / :1592-1593")
 K_TILED_STATS = (1, "gemm_engine.h:611-613, EpStoreStatsT::put4")
 K_TILED_BWD = (1, "gemm_engine.h:632-633, bn_bwd_contrib")
 K_PWS_FWD = (1, "pw_stream.hip:489")

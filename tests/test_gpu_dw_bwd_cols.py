@@ -80,6 +80,70 @@ def test_two_columns_match_one(N, H, W, C, relu, bn_in, stats, resid, with_dx, d
         assert float((s2 - s1).norm() / s1.norm()) < 1e-12
 
 
+# The smallest shapes that select each block geometry: W < 12 (one column per thread either way),
+# a 32-column strip (C / 4 = 16) and a 16-column strip (C / 4 = 32, 14 columns)
+SMALL = [(7, 16), (13, 64), (14, 128)]
+
+
+@pytest.mark.parametrize("W,C", SMALL)
+@pytest.mark.parametrize("resid", [False, True], ids=["nores", "res"])
+@pytest.mark.parametrize("bn_in,stats", [(True, True), (True, False), (False, False)], ids=["part", "bn", "plain"])
+@pytest.mark.parametrize("relu", [0, 1], ids=["norelu", "relu"])
+@pytest.mark.parametrize("dt", [BF16, torch.float32], ids=["bf16", "f32"])
+def test_every_launch_form_at_small_shapes(W, C, relu, bn_in, stats, resid, dt):
+    """Every kernel the entry points' launch ladder can pick (storage type x partials / input BN /
+    neither x output ReLU x residual x columns per thread), checked as test_two_columns_match_one."""
+    test_two_columns_match_one(2, 5, W, C, relu, bn_in, stats, resid, True, dt)
+
+
+@pytest.mark.parametrize("W,C", SMALL)
+@pytest.mark.parametrize("stored_mask", [False, True], ids=["nomask", "mask"])
+@pytest.mark.parametrize("resid", [False, True], ids=["nores", "res"])
+@pytest.mark.parametrize("relu", [0, 1], ids=["norelu", "relu"])
+@pytest.mark.parametrize("cols", [1, 2])
+def test_join_forms_at_small_shapes(W, C, relu, resid, stored_mask, cols):
+    """The join entry (dk_dwconv_bwd_bnbwd_join_f32) in every form its launch ladder can pick, against the
+    plain entry on the same inputs: dx = (the plain entry's dx, residual included) x (y > 0) bit for bit,
+    the weight gradient to fp32 rounding, and the join BatchNorm's partial sums against their fp64
+    reference within test_gpu_partial_rows.py's bound."""
+    from tests._partials import K_DW_BWD_JOIN, bwd_ref
+    N, H = 2, 5
+    rng = np.random.RandomState(W + C + 2 * relu + 3 * resid + 5 * stored_mask)
+    g, x1 = _h(rng, N, C, H, W, torch.float32), _h(rng, N, C, H, W, torch.float32)
+    y = torch.relu(_h(rng, N, C, H, W, torch.float32))
+    mask = (y > 0).to(torch.uint8).contiguous(memory_format=torch.channels_last)
+    jx = _h(rng, N, C, H, W, torch.float32)
+    jp = [torch.as_tensor(v.astype(np.float32), device="cuda") for v in (rng.randn(C) * 0.3, rng.rand(C) + 0.5)]
+    res = _h(rng, N, C, H, W, torch.float32) if resid else None
+    po = _bn(C, rng)
+    k12 = torch.as_tensor(rng.randn(2 * C).astype(np.float32) * 0.1, device="cuda")
+    wd = torch.as_tensor(rng.randn(C, 3, 3).astype(np.float32) * 0.3, device="cuda")
+    _, dx0, dw0, _ = _run(cols, g, x1, y, wd, po, k12, relu, None, 0, res, True, False)
+    lib.dk_debug_set_gemm_config(COLS_KNOB, cols)
+    try:
+        rows = lib.dk_dwconv_bwd_bnbwd_stats_rows(N, H, W, C)
+        nb = lib.dk_dwconv_bwd_bnbwd_workspace_bytes(N, H, W, C, 3, 3)
+        ws = torch.empty(nb // 4 + 64, dtype=torch.float32, device="cuda")
+        part = torch.full((rows, 2, C), float("nan"), dtype=torch.float64, device="cuda")
+        dx, dw = torch.full_like(y, float("nan")), torch.full_like(wd, float("nan"))
+        rc = lib.dk_dwconv_bwd_bnbwd_join_f32(g.data_ptr(), x1.data_ptr(), N, H, W, C, *(t.data_ptr() for t in po), relu,
+                                              k12.data_ptr(), y.data_ptr(), wd.data_ptr(), 3, 3, 1, 1e-3, dw.data_ptr(),
+                                              dx.data_ptr(), res.data_ptr() if resid else 0,
+                                              mask.data_ptr() if stored_mask else 0, jx.data_ptr(), jp[0].data_ptr(),
+                                              jp[1].data_ptr(), part.data_ptr(), ws.data_ptr(), nb, stream_handle())
+        torch.cuda.synchronize()
+    finally:
+        lib.dk_debug_set_gemm_config(COLS_KNOB, -1)
+    assert rc in (0, 10100), rc
+    assert torch.equal(dx, dx0 * (y > 0))
+    err = float((dw - dw0).norm() / dw0.norm())
+    assert err < 2e-6, err
+    ref, mag = bwd_ref(dx, jx, jp, 0)
+    bound = (K_DW_BWD_JOIN[0] + 4) * 2.0 ** -24 * mag
+    assert float(mag.max()) > 0
+    assert float(((part.sum(0) - ref).abs() / bound.clamp_min(1e-300)).max()) < 1.0
+
+
 def test_geometry():
     """Two columns per thread where the width allows (W >= 12, C / 4 a multiple of 16), with the
     strip width that pads the row least; one column otherwise."""

@@ -29,13 +29,14 @@ def _bn(C, rng):
             (rng.randn(C) * 0.3, rng.rand(C) + 0.5, 1 + 0.3 * rng.randn(C), 0.2 * rng.randn(C))]
 
 
-def _fused(dt, g, x1, x, po, relu, k12, wd, pi, bn_relu, res, with_dx, l2):
+def _fused(dt, g, x1, x, po, relu, k12, wd, pi, bn_relu, res, with_dx, l2, with_part=True):
     N, C, H, W = x.shape
     OH, OW = x1.shape[2], x1.shape[3]
     rows = lib.dk_dwconv_bwd_s2_stats_rows(N, H, W, C)
     assert rows > 0
     nb = lib.dk_dwconv_bwd_s2_workspace_bytes(N, H, W, C)
-    part = torch.full((rows, 2, C), float("nan"), dtype=torch.float64, device="cuda") if pi is not None else None
+    part = (torch.full((rows, 2, C), float("nan"), dtype=torch.float64, device="cuda")
+            if pi is not None and with_part else None)
     dx = torch.full_like(x, float("nan")) if with_dx else None
     dw = torch.full_like(wd, float("nan"))
     fn = lib.dk_dwconv_bwd_s2_bnbwd_bf16 if dt == BF16 else lib.dk_dwconv_bwd_s2_bnbwd_f32
@@ -113,6 +114,43 @@ def test_s2_fused_bf16_is_rounded_f32(N, H, W, C, relu, bn_relu):
     assert torch.equal(dwh, dwf)
     s0, s1 = pf.sum(0), ph.sum(0)  # partials over the stored (rounded) dx: bf16 rounding apart
     assert float((s1 - s0).norm() / s0.norm()) < 1e-2
+
+
+@pytest.mark.parametrize("C", [16, 64])
+@pytest.mark.parametrize("resid", [False, True], ids=["nores", "res"])
+@pytest.mark.parametrize("mode", ["part", "bn", "plain"])
+@pytest.mark.parametrize("relu", [0, 1], ids=["norelu", "relu"])
+def test_s2_every_launch_form_at_a_small_shape(C, relu, mode, resid):
+    """Every kernel the fp32 / bf16 entry points' launch ladder can pick (partials / input BN alone /
+    neither x output ReLU x residual) at 2 x 7 x 9: the fp32 forms with and without partials as
+    test_s2_fused_matches_unfused_f32; the input BN without partials equals the form with them (dx bit
+    for bit, dW to fp32 rounding); bf16 as test_s2_fused_bf16_is_rounded_f32."""
+    N, H, W = 2, 7, 9
+    if mode != "bn":
+        test_s2_fused_matches_unfused_f32(N, H, W, C, relu, mode == "part", relu, resid)
+    rng = np.random.RandomState(C + relu + 3 * resid + 5 * len(mode))
+    OH, OW = (H + 1) // 2, (W + 1) // 2
+    g, x1 = _t(rng, (N, C, OH, OW), BF16), _t(rng, (N, C, OH, OW), BF16)
+    x = _t(rng, (N, C, H, W), BF16)
+    res = _t(rng, (N, C, H, W), BF16) if resid else None
+    po, pi = _bn(C, rng), (_bn(C, rng) if mode != "plain" else None)
+    k12 = torch.as_tensor(rng.randn(2 * C).astype(np.float32) * 0.1, device="cuda")
+    wd = torch.as_tensor(rng.randn(C, 3, 3).astype(np.float32) * 0.3, device="cuda")
+    f32 = [t.float().contiguous(memory_format=torch.channels_last) for t in (g, x1, x)]
+    resf = res.float().contiguous(memory_format=torch.channels_last) if resid else None
+    part = mode == "part"
+    dxh, dwh, ph = _fused(BF16, g, x1, x, po, relu, k12, wd, pi, relu, res, True, 0.0, part)
+    dxf, dwf, pf = _fused(torch.float32, *f32, po, relu, k12, wd, pi, relu, resf, True, 0.0, part)
+    assert torch.equal(dxh, dxf.to(BF16))
+    assert torch.equal(dwh, dwf)
+    if part:
+        s0, s1 = pf.sum(0), ph.sum(0)
+        assert float((s1 - s0).norm() / s0.norm()) < 1e-2
+    if mode == "bn":
+        dxp, dwp, _ = _fused(torch.float32, *f32, po, relu, k12, wd, pi, relu, resf, True, 0.0, True)
+        assert torch.equal(dxf, dxp)
+        err = float((dwf - dwp).norm() / dwp.norm())
+        assert err < 2e-6, err
 
 
 def test_s2_rejects_other_shapes():

@@ -24,7 +24,7 @@ from ..layers.pointwise_convolution import PointwiseConvLayer  # noqa: F401
 from ..layers.pooling import GlobalAveragePoolingLayer  # noqa: F401
 from ..layers.residual_block import ResidualBlock  # noqa: F401
 from .._hip import async_weight_grads
-from .._tensor import as_device
+from .._tensor import act_dtype, as_device
 
 
 class FeedForwardNetwork:
@@ -173,6 +173,36 @@ class FeedForwardNetwork:
             test_correct_total += np.sum(np.asarray(y_test_batch) ==
                                          np.argmax(batch_scores.cpu().numpy(), axis=1))
         return float(test_correct_total) / test_set_size
+
+    def class_activation_maps(self, X, top=3, feature_layer="res8", dense_layer="dense1", feature_test_mode=True):
+        """Class activation maps of the `top` best classes of every image of the batch X (fp32 or bf16
+        (N, 3, H, W), channels B, G, R, minus 128 as the preprocessor delivers it), on the GPU
+        (dorknet_amd/cam.py; the reference's examples/imagenet_dogs_225_resnet_18_depsep_CAM.py:62-87).
+        Returns (class_idx int32 (N, top), masks fp32 (N, top, H, W), overlays uint8 (N, top, H, W, 3) BGR).
+
+        The scores come from forward(X, None, test_mode=True), the features from
+        forward(X, None, test_mode=feature_test_mode, terminal_layer_name=feature_layer), the weights
+        from the DenseLayer named `dense_layer`.  The reference's script takes its features with
+        test_mode=False, i.e. with the batch statistics of the single image it feeds; the default here
+        is True (the running statistics, as for the scores).  feature_test_mode=False on a batch of one
+        image gives the reference's behaviour (and updates the running statistics, as it does there)."""
+        import torch
+        from ..cam import class_activation_maps, top_classes
+        dense = next((l for l in self.layers if l.layer_name == dense_layer), None)
+        if not isinstance(dense, DenseLayer):
+            raise ValueError("class_activation_maps: the network has no DenseLayer named {!r}".format(dense_layer))
+        if not any(l.layer_name == feature_layer for l in self.layers):
+            raise ValueError("class_activation_maps: the network has no layer named {!r}".format(feature_layer))
+        X = as_device(X, act_dtype(X))
+        _, scores = self.forward(X, None, test_mode=True)
+        _, features = self.forward(X, None, test_mode=feature_test_mode, terminal_layer_name=feature_layer)
+        if features.dim() != 4:
+            raise ValueError("class_activation_maps: the output of layer {!r} is not a 4-D feature map".format(
+                feature_layer))
+        class_idx = top_classes(scores, top)
+        images = X if X.dtype == torch.float32 else X.float()   # bf16 widens exactly
+        masks, overlays = class_activation_maps(features, dense.learned_params["weights"], class_idx, images=images)
+        return class_idx, masks, overlays
 
     def save_weights_to_h5(self, fname):
         from .checkpoint import open_h5

@@ -584,6 +584,30 @@ int dk_colsum_f32(const float* in, int M, int N, float* out, void* ws, size_t ws
 int dk_nchw_to_nhwc_f32(const float* x, int N, int C, int H, int W, int Cp, float* y, void* stream);
 int dk_nhwc_unpad_f32(const float* x, long long P, int Cp, int C, float* y, void* stream);
 
+/* ---------------------------------------------------------------------------------------
+ * Class activation maps (dorknet_amd/csrc/cam.hip), replacing returnCAM and
+ * show_cam_on_image of examples/imagenet_dogs_225_resnet_18_depsep_CAM.py:13-49 for N images x K
+ * classes in one launch (one workgroup per map), pinned bit for bit by tests/_cam_ref.py:
+ *   feat       NHWC [N][h][w][C], fp32 (dk_cam_f32) or bf16 bits widened exactly on load (dk_cam_bf16);
+ *   weights    the dense layer's fp32 (C, classes) array; class j is column j;
+ *   class_idx  device int32 [N][K]; an index outside [0, classes) is clamped into range;
+ *   image      fp32 NCHW [N][3][H][W] (channels B, G, R), or NULL;  shift: added to it (the reference: 128);
+ *   mask       fp32 [N][K][H][W] (the reference's cam_img), or NULL;
+ *   overlay    uint8 [N][K][H][W][3] (show_cam_on_image), or NULL.
+ * Per map: the dot product over C (64 partial sums over channels j, j + 64, ... in ascending order, then
+ * s_j += s_{j+d} for d = 32 ... 1), cv2.resize INTER_LINEAR in fp32 to H x W, max(., 0), minus the minimum,
+ * divided by (max - min) if that is > 0; heat = JET[(uint8)(255 m)], o = heat + (image + shift),
+ * overlay = (uint8)(255 (o / max o)), clamped to [0, 255].  IEEE fp32, one rounding per operation.
+ * 10001, and nothing is launched, for: h * w > 1024; N, K, h, w, H, W, C or classes < 1; a NULL feat,
+ * weights or class_idx; both outputs NULL; an overlay without an image; H * W > 2^31 - 1 - 2048.
+ *
+ * dk_topk_rows_f32: np.argsort(row)[::-1][:K] for each row of scores [N][classes] -> idx_out int32 [N][K];
+ * equal scores put the higher index first; 1 <= K <= min(classes, 16), else 10001.  NaN scores give
+ * unspecified indices inside [0, classes). */
+int dk_cam_f32(const float* feat, int N, int h, int w, int C, const float* weights, int classes, const int* class_idx, int K, const float* image, int H, int W, float shift, float* mask, uint8_t* overlay, void* stream);
+int dk_cam_bf16(const uint16_t* feat, int N, int h, int w, int C, const float* weights, int classes, const int* class_idx, int K, const float* image, int H, int W, float shift, float* mask, uint8_t* overlay, void* stream);
+int dk_topk_rows_f32(const float* scores, int N, int classes, int K, int* idx_out, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -274,101 +274,93 @@ int splitk_reduce(const float* ws, int splits, int M, int N, float* out, const f
 int wgrad_reduce(const float* ws, int splits, int M, int N, float* out, const float* w, float l2, hipStream_t st);
 
 
-// Streaming pointwise kernels (pw_stream.hip) for the K = C = 64 shapes.
-bool pw_stream_enabled();  // knob kKnobPwStream (default 1; 0 = the tiled engine everywhere, for A/B runs)
-bool pw_stream_dgrad_ok(int K, int C, int M);
-int pw_stream_dgrad_rows(int M);
-bool pw_stream_bwd_ok(int K, int C, int M);
-int pw_stream_bwd_rows(int M);
+// The pointwise kernel families (pw_stream.hip, pw_deep.hip and their bf16 twins; host layer:
+// pw_launch.h).  One plan per (family, operation), a function of the shape and the knobs only:
+// rows = the partial rows the launch writes (its gridDim.x), slices = their channel slices (fold_take;
+// gridDim.y); rows == 0: the family does not take the shape.  The queries and the launches read the
+// same plan; a launcher is handed it and launches once.
+struct PwPlan {
+  int rows, slices;
+};
 struct FoldTail;  // fold_tail.h
-int pw_stream_bwd_fused(const float* g, const float* bn_x, int M, const float* om, const float* ois,
-                        const float* og, const float* ob, int orelu, const float* k12, const float* w, float* dx,
-                        const float* res, const float* x, const float* im, const float* iis, const float* ig,
-                        const float* ib, int irelu, double* part, const float* bm, const float* bis,
-                        const float* bgm, const float* bbt, int brelu, float* wpart, hipStream_t st,
-                        const struct FoldTail* ft = nullptr, const int* lattice = nullptr);
-bool pw_stream_fwd_ok(int K, int C, int M, size_t xbytes);
-int pw_stream_fwd_rows(int M, int K);
+bool pw_stream_enabled();  // knob kKnobPwStream (default 1; 0 = the tiled engine everywhere, for A/B runs)
+
+// fp32 streaming kernels (pw_stream.hip): K = C = 64, the forward also K = C = 128.
+PwPlan pw_stream_fwd_plan(int M, int K, int C, size_t xbytes);
+PwPlan pw_stream_dgrad_plan(int M, int K, int C);
+PwPlan pw_stream_bwd_plan(int M, int K, int C);
 int pw_stream_fwd(const float* x, int N, int H, int W, int stride, int OH, int OW, const float* w, int KC,
                   const float* bias, float* y, const float* im, const float* iis, const float* ig,
-                  const float* ib, int irelu, double* part, hipStream_t st, const struct FoldTail* ft = nullptr);
+                  const float* ib, int irelu, double* part, PwPlan plan, hipStream_t st,
+                  const struct FoldTail* ft = nullptr);
 int pw_stream_dgrad_bnbwd(const float* g, const float* bn_x, int M, const float* om, const float* ois,
                           const float* og, const float* ob, int orelu, const float* k12, float* dy_out,
                           const float* w, float* dx, const float* res, const float* x, const float* im,
                           const float* iis, const float* ig, const float* ib, int irelu, double* part,
-                          hipStream_t st, const struct FoldTail* ft = nullptr);
+                          PwPlan plan, hipStream_t st, const struct FoldTail* ft = nullptr);
+int pw_stream_bwd_fused(const float* g, const float* bn_x, int M, const float* om, const float* ois,
+                        const float* og, const float* ob, int orelu, const float* k12, const float* w, float* dx,
+                        const float* res, const float* x, const float* im, const float* iis, const float* ig,
+                        const float* ib, int irelu, double* part, const float* bm, const float* bis,
+                        const float* bgm, const float* bbt, int brelu, float* wpart, PwPlan plan, hipStream_t st,
+                        const struct FoldTail* ft = nullptr, const int* lattice = nullptr);
 
-// fp32 deep streaming pointwise kernels (pw_deep.hip): reduction 64-512 with 128+ channels on a side.
-bool pw_deep_fwd_ok(int K, int C, int M, size_t xbytes);
-int pw_deep_fwd_rows(int M, int K, int C);
-int pw_deep_fwd_slices(int M, int K, int C);
+// fp32 deep kernels (pw_deep.hip): reduction 64-512 with 128+ channels on a side; the fused backward
+// (dgrad + weight gradient in one pass, dy never stored) at K in {128, 256}.
+PwPlan pw_deep_fwd_plan(int M, int K, int C, size_t xbytes);
+PwPlan pw_deep_dgrad_plan(int M, int K, int C);
+PwPlan pw_deep_bwd_plan(int M, int K, int C);
 int pw_deep_fwd(const float* x, int N, int H, int W, int stride, int OH, int OW, const float* w, int K, int C,
                 const float* bias, float* y, const float* im, const float* iis, const float* ig, const float* ib,
-                int irelu, double* part, hipStream_t st, const struct FoldTail* ft = nullptr);
-bool pw_deep_dgrad_ok(int K, int C, int M);
-int pw_deep_dgrad_rows(int M, int K, int C);
-int pw_deep_dgrad_slices(int M, int K, int C);
-// The fused deep backward (dgrad + weight gradient in one pass, dy never stored): K in {128, 256}.
-bool pw_deep_bwd_ok(int K, int C, int M);
-int pw_deep_bwd_rows(int M, int K, int C);
-int pw_deep_bwd_slices(int M, int K, int C);
-int pw_deep_dgrad_plain(const float* dy, int M, int K, int C, const float* w, float* dx, hipStream_t st);
-
-int pw_deep_bwd_bnbwd(const float* g, const float* bn_x, int M, int K, int C, const float* om, const float* ois,
-                      const float* og, const float* ob, int orelu, const float* k12, const float* w, float* dx,
-                      const float* res, const float* x, const float* im, const float* iis, const float* ig,
-                      const float* ib, int irelu, double* part, float* wpart, hipStream_t st,
-                      const struct FoldTail* ft = nullptr);
-// bf16 weight-stationary deep pointwise kernels (pw_deep_bf16.hip), used by the pw_stream_bf16 entries.
-bool pw_deep16_fwd_ok(int K, int C, int M);
-bool pw_deep16_dgrad_ok(int K, int C, int M);
-int pw_deep16_fwd_rows(int M, int K, int C);
-int pw_deep16_dgrad_rows(int M, int K, int C);
-int pw_deep16_fwd(const bf16_t* x, int M, const float* w, int K, int C, const float* bias, bf16_t* y, const float* im,
-                  const float* iis, const float* ig, const float* ib, int irelu, double* part, hipStream_t st,
-                  const struct FoldTail* ft);
-int pw_deep16_dgrad_bnbwd(const bf16_t* g, const bf16_t* bn_x, int M, int K, int C, const float* om, const float* ois,
-                          const float* og, const float* ob, int orelu, const float* k12, bf16_t* dy_out, const float* w,
-                          bf16_t* dx, const bf16_t* res, const bf16_t* x, const float* im, const float* iis,
-                          const float* ig, const float* ib, int irelu, double* part, hipStream_t st,
-                          const struct FoldTail* ft);
+                int irelu, double* part, PwPlan plan, hipStream_t st, const struct FoldTail* ft = nullptr);
 int pw_deep_dgrad_bnbwd(const float* g, const float* bn_x, int M, int K, int C, const float* om, const float* ois,
                         const float* og, const float* ob, int orelu, const float* k12, float* dy_out, const float* w,
                         float* dx, const float* res, const float* x, const float* im, const float* iis,
-                        const float* ig, const float* ib, int irelu, double* part, hipStream_t st,
+                        const float* ig, const float* ib, int irelu, double* part, PwPlan plan, hipStream_t st,
                         const struct FoldTail* ft = nullptr);
+int pw_deep_dgrad_plain(const float* dy, int M, int K, int C, const float* w, float* dx, PwPlan plan, hipStream_t st);
+int pw_deep_bwd_bnbwd(const float* g, const float* bn_x, int M, int K, int C, const float* om, const float* ois,
+                      const float* og, const float* ob, int orelu, const float* k12, const float* w, float* dx,
+                      const float* res, const float* x, const float* im, const float* iis, const float* ig,
+                      const float* ib, int irelu, double* part, float* wpart, PwPlan plan, hipStream_t st,
+                      const struct FoldTail* ft = nullptr);
 
-// the fused bf16 deep backward (pw_deep_bf16.hip bwd_kernel): K in {128, 256}
-bool pw_deep16_bwd_ok(int K, int C, int M);
-int pw_deep16_bwd_rows(int M, int K, int C);
-int pw_deep16_bwd_slices(int M, int K, int C);
-int pw_deep16_bwd_fused(const bf16_t* g, const bf16_t* bn_x, int M, int K, int C, const float* om, const float* ois,
-                        const float* og, const float* ob, int orelu, const float* k12, const float* w, bf16_t* dx,
-                        const bf16_t* res, const bf16_t* x, const float* im, const float* iis, const float* ig,
-                        const float* ib, int irelu, double* part, float* wpart, hipStream_t st,
-                        const struct FoldTail* ft = nullptr);
-// bf16 streaming pointwise kernels (pw_stream_bf16.hip, BASELINE config 5): K, C in {64, 128}.
-bool pw_stream_bf16_fwd_ok(int K, int C, int M);
-int pw_stream_bf16_fwd_rows(int M, int K, int C);
+// bf16 streaming kernels (pw_stream_bf16.hip, BASELINE config 5): K, C in {64, 128}; the fused
+// backward at K = C = 64.
+PwPlan pw_stream_bf16_fwd_plan(int M, int K, int C);
+PwPlan pw_stream_bf16_dgrad_plan(int M, int K, int C);
+PwPlan pw_stream_bf16_bwd_plan(int M, int K, int C);
 int pw_stream_bf16_fwd(const bf16_t* x, int M, const float* w, int K, int C, const float* bias, bf16_t* y,
                        const float* im, const float* iis, const float* ig, const float* ib, int irelu, double* part,
-                       hipStream_t st, const struct FoldTail* ft = nullptr);
-bool pw_stream_bf16_dgrad_ok(int K, int C, int M);
-int pw_stream_bf16_dgrad_rows(int M, int K, int C);
+                       PwPlan plan, hipStream_t st, const struct FoldTail* ft = nullptr);
 int pw_stream_bf16_dgrad_bnbwd(const bf16_t* g, const bf16_t* bn_x, int M, int K, int C, const float* om,
                                const float* ois, const float* og, const float* ob, int orelu, const float* k12,
                                bf16_t* dy_out, const float* w, bf16_t* dx, const bf16_t* res, const bf16_t* x,
                                const float* im, const float* iis, const float* ig, const float* ib, int irelu,
-                               double* part, hipStream_t st, const struct FoldTail* ft = nullptr);
-int pw_stream_bf16_fwd_slices(int K, int C);    // channel slices of the partial rows (fold_take)
-// the fused bf16 backward (dgrad + weight gradient, dy never stored) for K = C = 64
-bool pw_stream_bf16_bwd_ok(int K, int C, int M);
-int pw_stream_bf16_bwd_rows(int M);
+                               double* part, PwPlan plan, hipStream_t st, const struct FoldTail* ft = nullptr);
 int pw_stream_bf16_bwd_fused(const bf16_t* g, const bf16_t* bn_x, int M, const float* om, const float* ois,
                              const float* og, const float* ob, int orelu, const float* k12, const float* w, bf16_t* dx,
                              const bf16_t* res, const bf16_t* x, const float* im, const float* iis, const float* ig,
-                             const float* ib, int irelu, double* part, float* wpart, hipStream_t st,
+                             const float* ib, int irelu, double* part, float* wpart, PwPlan plan, hipStream_t st,
                              const struct FoldTail* ft = nullptr);
-int pw_stream_bf16_dgrad_slices(int K, int C);
+
+// bf16 weight-stationary deep kernels (pw_deep_bf16.hip): reduction 128-512 with 256+ channels on a
+// side; the fused backward at K in {128, 256}.
+PwPlan pw_deep16_fwd_plan(int M, int K, int C);
+PwPlan pw_deep16_dgrad_plan(int M, int K, int C);
+PwPlan pw_deep16_bwd_plan(int M, int K, int C);
+int pw_deep16_fwd(const bf16_t* x, int M, const float* w, int K, int C, const float* bias, bf16_t* y, const float* im,
+                  const float* iis, const float* ig, const float* ib, int irelu, double* part, PwPlan plan,
+                  hipStream_t st, const struct FoldTail* ft = nullptr);
+int pw_deep16_dgrad_bnbwd(const bf16_t* g, const bf16_t* bn_x, int M, int K, int C, const float* om, const float* ois,
+                          const float* og, const float* ob, int orelu, const float* k12, bf16_t* dy_out, const float* w,
+                          bf16_t* dx, const bf16_t* res, const bf16_t* x, const float* im, const float* iis,
+                          const float* ig, const float* ib, int irelu, double* part, PwPlan plan, hipStream_t st,
+                          const struct FoldTail* ft = nullptr);
+int pw_deep16_bwd_fused(const bf16_t* g, const bf16_t* bn_x, int M, int K, int C, const float* om, const float* ois,
+                        const float* og, const float* ob, int orelu, const float* k12, const float* w, bf16_t* dx,
+                        const bf16_t* res, const bf16_t* x, const float* im, const float* iis, const float* ig,
+                        const float* ib, int irelu, double* part, float* wpart, PwPlan plan, hipStream_t st,
+                        const struct FoldTail* ft = nullptr);
 
 }  // namespace dk

@@ -196,4 +196,23 @@ bool fold_take(const void* part, int nrows, int C, int nslices, FoldTail* ft);
 // The status an entry point returns after a launch that took an arming (DK_FOLDED on success).
 int fold_status(int rc, const FoldTail& ft);
 
+// A planned pointwise launch that writes part[plan.rows][2][C] (nullable): take the arming, run
+// launch(ft or nullptr) -> status, report the fold.
+template <class L>
+static inline int pw_fold_launch(const void* part, PwPlan plan, int C, L launch) {
+  FoldTail ft;
+  if (part) fold_take(part, plan.rows, C, plan.slices, &ft);
+  return fold_status(launch(part ? &ft : nullptr), part ? ft : FoldTail{});
+}
+// The same for a fused backward, whose launch leaves plan.rows weight-gradient partials [K][C] in
+// wp: they are reduced into dw (+ l2 w) in a fixed order after it.
+template <class L>
+static inline int pw_bwd_fold_launch(const void* part, PwPlan plan, int K, int C, const float* wp, const float* w,
+                                     float l2, float* dw, hipStream_t st, L launch) {
+  return pw_fold_launch(part, plan, C, [&](const FoldTail* ft) {
+    const int rc = launch(ft);
+    return rc ? rc : wgrad_reduce(wp, plan.rows, K, C, dw, l2 != 0.f ? w : nullptr, l2, st);
+  });
+}
+
 }  // namespace dk

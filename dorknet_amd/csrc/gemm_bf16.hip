@@ -1,6 +1,7 @@
 // bf16 pointwise entry points (BASELINE config 5) and bf16 dense-convolution entry points on the
 // implicit-GEMM engine's bf16 MFMA mode (gemm_engine.h).
 #include "gemm_engine.h"
+#include "pw_launch.h"
 
 using namespace dk;
 
@@ -24,14 +25,45 @@ static inline ImgDescE<bf16_t, true> img1_h(const bf16_t* x, int N, int H, int W
                                            1, 1, sa, 1, 0, 0, M});
 }
 static inline bool al8(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 7) == 0; }
+
+// The path of the three bf16 pointwise operations, each read by its row query and its entry: the
+// weight-stationary deep kernels (pw_deep_bf16.hip: a side of 256+) before the streaming ones
+// (pw_stream_bf16.hip: K, C in {64, 128}; the fused backward K = C = 64) before the tiled engine.
+static PwChoice pw16_fwd_choice(int M, int K, int C) {
+  return pw_choice(pw_deep16_fwd_plan(M, K, C), pw_stream_bf16_fwd_plan(M, K, C));
+}
+static PwChoice pw16_dgrad_choice(int M, int K, int C) {
+  return pw_choice(pw_deep16_dgrad_plan(M, K, C), pw_stream_bf16_dgrad_plan(M, K, C));
+}
+static PwChoice pw16_bwd_choice(int M, int K, int C) {
+  return pw_choice(pw_deep16_bwd_plan(M, K, C), pw_stream_bf16_bwd_plan(M, K, C));
+}
+// Launch-only conditions (what the row queries cannot see; DESIGN.md lists them).  A forward or dgrad
+// call that fails one of these runs the tiled engine although its shape has a deep or streaming plan:
+// with partials, the rows written are then the tiled engine's, not the rows the query reported.
+//   * forward: stride 1 on an unpadded grid (dk_pwconv_fwd_bf16_strided_stats_rows is the query that
+//     knows the stride), x on a 16-byte boundary (the entry asks for 8), a given input BatchNorm
+//     complete and aligned (the tiled engine then refuses the call);
+//   * dgrad: g, bn_x and a given dy_out on 16-byte boundaries (the entry asks for 8), and with
+//     partials the input BatchNorm complete and aligned (the tiled engine then refuses the call).
+static bool pw16_fwd_launch_ok(const bf16_t* x, int stride, int H, int W, int OH, int OW, const float* bn_mean,
+                               const float* bn_invstd, const float* bn_gamma, const float* bn_beta) {
+  return stride == 1 && H == OH && W == OW && aligned16(x) && (!bn_mean || bn_ok(bn_mean, bn_invstd, bn_gamma, bn_beta));
+}
+static bool pw16_dgrad_launch_ok(const bf16_t* g, const bf16_t* bn_x, const bf16_t* dy_out, const double* part,
+                                 const float* bn_mean, const float* bn_invstd, const float* bn_gamma,
+                                 const float* bn_beta) {
+  return aligned16(g) && aligned16(bn_x) && (!dy_out || aligned16(dy_out)) &&
+         (!part || bn_ok(bn_mean, bn_invstd, bn_gamma, bn_beta));
+}
 }  // namespace dk
 
-// partial-statistics rows of dk_pwconv_fwd_ex_bf16: one per streaming block (K, C in {64, 128},
-// pw_stream_bf16.hip), else one per M tile of the tiled engine
+// partial-statistics rows of dk_pwconv_fwd_ex_bf16: the deep or streaming plan's, else one per M tile
+// of the tiled engine
 DK_API int dk_pwconv_fwd_bf16_stats_rows(int N, int OH, int OW, int K, int C) {
   const int M = N * OH * OW;
-  if (pw_stream_bf16_fwd_ok(K, C, M)) return pw_stream_bf16_fwd_rows(M, K, C);
-  return stats_rows(M, K, C, kRowFwdH, kMfBf16);
+  const PwChoice c = pw16_fwd_choice(M, K, C);
+  return c.path == kPwTiled ? stats_rows(M, K, C, kRowFwdH, kMfBf16) : c.plan.rows;
 }
 // The same for any stride: the streaming kernels take stride 1 only, a strided launch (the
 // N x OH x OW output lattice of a larger input) always runs the tiled engine -- one row per M tile.
@@ -47,15 +79,15 @@ DK_API int dk_pwconv_fwd_ex_bf16(const bf16_t* x, int N, int H, int W, int C, co
   if (C % 4 || K % 4 || !al8(x) || !al8(y) || !aligned16(w_kc) || (bias && !aligned16(bias))) return DK_ERR_ARGS;
   if (!fits((size_t)N * H * W * C * 4) || !fits((size_t)N * OH * OW * K * 4)) return DK_ERR_ARGS;
   const hipStream_t st = as_stream(stream);
-  if (stride == 1 && H == OH && W == OW && pw_stream_bf16_fwd_ok(K, C, N * OH * OW) && aligned16(x) &&
-      (!bn_mean || bn_ok(bn_mean, bn_invstd, bn_gamma, bn_beta))) {
-    // the streaming kernel (pw_stream_bf16.hip): bit-identical y, its own partial-row grouping
+  const PwChoice c = pw16_fwd_choice(N * OH * OW, K, C);
+  if (c.path != kPwTiled && pw16_fwd_launch_ok(x, stride, H, W, OH, OW, bn_mean, bn_invstd, bn_gamma, bn_beta)) {
+    // the deep (pw_deep_bf16.hip) or streaming (pw_stream_bf16.hip) kernel: bit-identical y, its own
+    // partial-row grouping
     const int M = N * OH * OW;
-    FoldTail ft;
-    if (stats) fold_take(stats, pw_stream_bf16_fwd_rows(M, K, C), K, pw_stream_bf16_fwd_slices(K, C), &ft);
-    return fold_status(pw_stream_bf16_fwd(x, M, w_kc, K, C, bias, y, bn_mean, bn_invstd, bn_gamma, bn_beta, bn_relu,
-                                          stats, st, stats ? &ft : nullptr),
-                       stats ? ft : FoldTail{});
+    return pw_fold_launch(stats, c.plan, K, [&](const FoldTail* ft) {
+      return (c.path == kPwDeep ? pw_deep16_fwd : pw_stream_bf16_fwd)(x, M, w_kc, K, C, bias, y, bn_mean, bn_invstd,
+                                                                     bn_gamma, bn_beta, bn_relu, stats, c.plan, st, ft);
+    });
   }
   const ImgDescE<bf16_t, true> a = img1_h(x, N, H, W, C, OH, OW, stride, N * OH * OW);
   const MatDesc b = mat(w_kc, K, C, K);
@@ -166,8 +198,8 @@ DK_API int dk_pwconv_wgrad_bnx_bf16(const bf16_t* dy, const bf16_t* x, int N, in
 
 DK_API int dk_pwconv_dgrad_bnbwd_bf16_stats_rows(int N, int OH, int OW, int K, int C) {
   const int M = N * OH * OW;
-  if (pw_stream_bf16_dgrad_ok(K, C, M)) return pw_stream_bf16_dgrad_rows(M, K, C);
-  return stats_rows(M, C, K, kRowBnBwd, kMfBf16);
+  const PwChoice c = pw16_dgrad_choice(M, K, C);
+  return c.path == kPwTiled ? stats_rows(M, C, K, kRowBnBwd, kMfBf16) : c.plan.rows;
 }
 
 // dk_pwconv_dgrad_bnbwd_f32 for bf16 storage: dy = the following BatchNorm's backward applied
@@ -186,16 +218,15 @@ DK_API int dk_pwconv_dgrad_bnbwd_bf16(const bf16_t* g, const bf16_t* bn_x, int N
   if ((residual && !al8(residual)) || (x && !al8(x))) return DK_ERR_ARGS;
   if (!fits((size_t)M * K * 4) || !fits((size_t)M * C * 4) || (part != nullptr) != (x != nullptr)) return DK_ERR_ARGS;
   if (!out_mean || !out_invstd || !out_gamma || !out_beta || !k12 || (size_t)K * 32 > 64 * 1024) return DK_ERR_ARGS;
-  if (pw_stream_bf16_dgrad_ok(K, C, M) && aligned16(g) && aligned16(bn_x) && (!dy_out || aligned16(dy_out)) &&
-      (!part || bn_ok(bn_mean, bn_invstd, bn_gamma, bn_beta))) {
-    // the streaming kernel (pw_stream_bf16.hip): bit-identical dy and dx, its own partial rows
-    FoldTail ft;
-    if (part) fold_take(part, pw_stream_bf16_dgrad_rows(M, K, C), C, pw_stream_bf16_dgrad_slices(K, C), &ft);
-    return fold_status(pw_stream_bf16_dgrad_bnbwd(g, bn_x, M, K, C, out_mean, out_invstd, out_gamma, out_beta,
-                                                  out_relu, k12, dy_out, w_kc, dx, residual, x, bn_mean, bn_invstd,
-                                                  bn_gamma, bn_beta, bn_relu, part, as_stream(stream),
-                                                  part ? &ft : nullptr),
-                       part ? ft : FoldTail{});
+  const PwChoice c = pw16_dgrad_choice(M, K, C);
+  if (c.path != kPwTiled && pw16_dgrad_launch_ok(g, bn_x, dy_out, part, bn_mean, bn_invstd, bn_gamma, bn_beta)) {
+    // the deep (pw_deep_bf16.hip) or streaming (pw_stream_bf16.hip) kernel: bit-identical dy and dx, its
+    // own partial rows
+    return pw_fold_launch(part, c.plan, C, [&](const FoldTail* ft) {
+      return (c.path == kPwDeep ? pw_deep16_dgrad_bnbwd : pw_stream_bf16_dgrad_bnbwd)(
+          g, bn_x, M, K, C, out_mean, out_invstd, out_gamma, out_beta, out_relu, k12, dy_out, w_kc, dx, residual, x,
+          bn_mean, bn_invstd, bn_gamma, bn_beta, bn_relu, part, c.plan, as_stream(stream), ft);
+    });
   }
   MatBwdDescE<bf16_t> a;
   static_cast<MatDescE<bf16_t>&>(a) = mat_h(g, M, K, M);
@@ -226,10 +257,7 @@ DK_API int dk_pwconv_dgrad_bnbwd_bf16(const bf16_t* g, const bf16_t* bn_x, int N
 // the workspace holds rows fp32 [K][C] weight-gradient partial rows.
 DK_API int dk_pwconv_bwd_fused_bf16_rows(int N, int OH, int OW, int K, int C) {
   if (N < 1 || OH < 1 || OW < 1 || (long long)N * OH * OW >= (1ll << 31)) return 0;
-  const int M = N * OH * OW;
-  if (pw_stream_bf16_bwd_ok(K, C, M)) return pw_stream_bf16_bwd_rows(M);
-  if (pw_deep16_bwd_ok(K, C, M)) return pw_deep16_bwd_rows(M, K, C);
-  return 0;
+  return pw16_bwd_choice(N * OH * OW, K, C).plan.rows;  // (no tiled form: 0)
 }
 
 DK_API size_t dk_pwconv_bwd_fused_bf16_workspace_bytes(int N, int OH, int OW, int K, int C) {
@@ -244,8 +272,10 @@ DK_API int dk_pwconv_bwd_bnbwd_bf16(const bf16_t* g, const bf16_t* bn_x, int N, 
                                     const float* bn_beta, int bn_relu, double* part, void* ws, size_t ws_bytes,
                                     void* stream) {
   const hipStream_t st = as_stream(stream);
-  const int rows = dk_pwconv_bwd_fused_bf16_rows(N, OH, OW, K, C);
-  if (rows <= 0) return DK_ERR_ARGS;
+  if (N < 1 || OH < 1 || OW < 1 || (long long)N * OH * OW >= (1ll << 31)) return DK_ERR_ARGS;
+  const int M = N * OH * OW;
+  const PwChoice c = pw16_bwd_choice(M, K, C);
+  if (c.path == kPwTiled) return DK_ERR_ARGS;
   if (!g || !bn_x || !x || !w_kc || !dw_kc || !dx || !out_mean || !out_invstd || !out_gamma || !out_beta || !k12)
     return DK_ERR_ARGS;
   if (part && !bn_mean) return DK_ERR_ARGS;
@@ -253,28 +283,19 @@ DK_API int dk_pwconv_bwd_bnbwd_bf16(const bf16_t* g, const bf16_t* bn_x, int N, 
   if (!aligned16(g) || !aligned16(bn_x) || !aligned16(w_kc) || !aligned16(ws) || !al8(x) || !al8(dx) ||
       (residual && !al8(residual)))
     return DK_ERR_ARGS;
-  if (ws_bytes < (size_t)rows * K * C * sizeof(float)) return DK_ERR_WORKSPACE;
-  const int M = N * OH * OW;
+  if (ws_bytes < (size_t)c.plan.rows * K * C * sizeof(float)) return DK_ERR_WORKSPACE;
   float* wp = static_cast<float*>(ws);
-  FoldTail ft;
-  if (!pw_stream_bf16_bwd_ok(K, C, M)) {
-    // K in {128, 256}: the weight-stationary kernel (pw_deep_bf16.hip); it needs the input BN's
-    // partials whenever there is an input BN
-    if ((bn_mean != nullptr) != (part != nullptr)) return DK_ERR_ARGS;
-    if (part) fold_take(part, rows, C, pw_deep16_bwd_slices(M, K, C), &ft);
-    int rc = pw_deep16_bwd_fused(g, bn_x, M, K, C, out_mean, out_invstd, out_gamma, out_beta, out_relu, k12, w_kc,
-                                 dx, residual, x, bn_mean, bn_invstd, bn_gamma, bn_beta, bn_relu, part, wp, st,
-                                 part ? &ft : nullptr);
-    if (rc) return rc;
-    return fold_status(wgrad_reduce(wp, rows, K, C, dw_kc, l2 != 0.f ? w_kc : nullptr, l2, st),
-                       part ? ft : FoldTail{});
-  }
-  if (part) fold_take(part, rows, C, 1, &ft);
-  int rc = pw_stream_bf16_bwd_fused(g, bn_x, M, out_mean, out_invstd, out_gamma, out_beta, out_relu, k12, w_kc, dx,
-                                    residual, x, bn_mean, bn_invstd, bn_gamma, bn_beta, bn_relu, part, wp, st,
-                                    part ? &ft : nullptr);
-  if (rc) return rc;
-  return fold_status(wgrad_reduce(wp, rows, K, C, dw_kc, l2 != 0.f ? w_kc : nullptr, l2, st), part ? ft : FoldTail{});
+  // K in {128, 256}: the weight-stationary kernel (pw_deep_bf16.hip); it needs the input BN's partials
+  // whenever there is an input BN
+  if (c.path == kPwDeep && (bn_mean != nullptr) != (part != nullptr)) return DK_ERR_ARGS;
+  return pw_bwd_fold_launch(part, c.plan, K, C, wp, w_kc, l2, dw_kc, st, [&](const FoldTail* ft) {
+    if (c.path == kPwDeep)
+      return pw_deep16_bwd_fused(g, bn_x, M, K, C, out_mean, out_invstd, out_gamma, out_beta, out_relu, k12, w_kc, dx,
+                                 residual, x, bn_mean, bn_invstd, bn_gamma, bn_beta, bn_relu, part, wp, c.plan, st, ft);
+    return pw_stream_bf16_bwd_fused(g, bn_x, M, out_mean, out_invstd, out_gamma, out_beta, out_relu, k12, w_kc, dx,
+                                    residual, x, bn_mean, bn_invstd, bn_gamma, bn_beta, bn_relu, part, wp, c.plan, st,
+                                    ft);
+  });
 }
 
 // ---------------------------------------------------------------------------------------

@@ -1,18 +1,38 @@
 // Pointwise (1x1) convolution entry points (layers/pointwise_convolution.py) on the implicit-GEMM
 // engine (gemm_engine.h) and the streaming kernels (pw_stream.hip).
 #include "gemm_engine.h"
+#include "pw_launch.h"
 
 using namespace dk;
+
+// The path of the forward (dk_pwconv_fwd_stats_rows, dk_pwconv_fwd_ex_f32) and of the dgrad with the
+// following BatchNorm's backward on load (dk_pwconv_dgrad_bnbwd_stats_rows, dk_pwconv_dgrad_bnbwd_f32,
+// and dk_pwconv_dgrad_f32's plain form, deep only).
+//
+// Launch-only conditions (what the row queries cannot see; DESIGN.md lists them):
+//   * xbytes: the queries pass 0, the launch the input's real extent -- which dk_pwconv_fwd_ex_f32 has
+//     already held below 2 GiB (fits), so the two choices agree;
+//   * a given input BatchNorm that is incomplete or misaligned (bn_ok): the deep paths refuse the
+//     call; the streaming forward leaves it to the tiled engine, which refuses it too.
+// So no fp32 call reaches a path whose row count differs from the query's.
+static PwChoice pw_fwd_choice(int M, int K, int C, size_t xbytes) {
+  return pw_choice(pw_deep_fwd_plan(M, K, C, xbytes), pw_stream_fwd_plan(M, K, C, xbytes));
+}
+static PwChoice pw_dgrad_choice(int M, int K, int C) {
+  return pw_choice(pw_deep_dgrad_plan(M, K, C), pw_stream_dgrad_plan(M, K, C));
+}
 
 // y[n,oh,ow,k] = sum_c x[n, oh*s, ow*s, c] * w[k][c] (+ bias)
 DK_API int dk_pwconv_fwd_f32(const float* x, int N, int H, int W, int C, const float* w_kc, int K, int stride,
                              const float* bias, float* y, int OH, int OW, void* stream) {
   if (!fits((size_t)N * H * W * C * 4)) return DK_ERR_ARGS;
-  if (C % 4 == 0 && aligned16(x) && aligned16(w_kc) &&
-      pw_deep_fwd_ok(K, C, N * OH * OW, (size_t)N * H * W * C * 4))
+  if (C % 4 == 0 && aligned16(x) && aligned16(w_kc)) {
     // the deep streaming kernel (pw_deep.hip), bit-identical y (the strided skip projections)
-    return pw_deep_fwd(x, N, H, W, stride, OH, OW, w_kc, K, C, bias, y, nullptr, nullptr, nullptr, nullptr, 0,
-                       nullptr, as_stream(stream));
+    const PwPlan deep = pw_deep_fwd_plan(N * OH * OW, K, C, (size_t)N * H * W * C * 4);
+    if (deep.rows)
+      return pw_deep_fwd(x, N, H, W, stride, OH, OW, w_kc, K, C, bias, y, nullptr, nullptr, nullptr, nullptr, 0,
+                         nullptr, deep, as_stream(stream));
+  }
   MatDesc b = mat(w_kc, K, C, K);
   EpStore ep = ep_store(y, K, bias);
   if (C % 4 || !aligned16(x) || !aligned16(w_kc)) {
@@ -38,10 +58,8 @@ DK_API int dk_pwconv_fwd_bnx_f32(const float* x, int N, int H, int W, int C, con
 
 DK_API int dk_pwconv_fwd_stats_rows(int N, int OH, int OW, int K, int C) {
   const int M = N * OH * OW;
-  // (the input extent does not change the choice for the shapes the network uses)
-  if (pw_deep_fwd_ok(K, C, M, 0)) return pw_deep_fwd_rows(M, K, C);
-  if (pw_stream_fwd_ok(K, C, M, 0)) return pw_stream_fwd_rows(M, K);
-  return stats_rows(M, K, C);
+  const PwChoice c = pw_fwd_choice(M, K, C, 0);
+  return c.path == kPwTiled ? stats_rows(M, K, C) : c.plan.rows;
 }
 
 DK_API int dk_pwconv_fwd_ex_f32(const float* x, int N, int H, int W, int C, const float* w_kc, int K, int stride,
@@ -49,26 +67,22 @@ DK_API int dk_pwconv_fwd_ex_f32(const float* x, int N, int H, int W, int C, cons
                                 const float* bn_invstd, const float* bn_gamma, const float* bn_beta, int bn_relu,
                                 double* stats, void* stream) {
   if (C % 4 || !aligned16(x) || !aligned16(w_kc) || !fits((size_t)N * H * W * C * 4)) return DK_ERR_ARGS;
-  if (pw_deep_fwd_ok(K, C, N * OH * OW, (size_t)N * H * W * C * 4)) {
+  const PwChoice c = pw_fwd_choice(N * OH * OW, K, C, (size_t)N * H * W * C * 4);
+  if (c.path == kPwDeep) {
     // the deep streaming kernel (pw_deep.hip): bit-identical y, its own partial rows and slices
     // (dk_pwconv_fwd_stats_rows sized the partials for it: no other path may take this call)
     if (bn_mean && !bn_ok(bn_mean, bn_invstd, bn_gamma, bn_beta)) return DK_ERR_ARGS;
-    const int M = N * OH * OW;
-    FoldTail ft;
-    if (stats) fold_take(stats, pw_deep_fwd_rows(M, K, C), K, pw_deep_fwd_slices(M, K, C), &ft);
-    return fold_status(pw_deep_fwd(x, N, H, W, stride, OH, OW, w_kc, K, C, bias, y, bn_mean, bn_invstd, bn_gamma,
-                                   bn_beta, bn_relu, stats, as_stream(stream), stats ? &ft : nullptr),
-                       stats ? ft : FoldTail{});
+    return pw_fold_launch(stats, c.plan, K, [&](const FoldTail* ft) {
+      return pw_deep_fwd(x, N, H, W, stride, OH, OW, w_kc, K, C, bias, y, bn_mean, bn_invstd, bn_gamma, bn_beta,
+                         bn_relu, stats, c.plan, as_stream(stream), ft);
+    });
   }
-  if (pw_stream_fwd_ok(K, C, N * OH * OW, (size_t)N * H * W * C * 4) && (!bn_mean || bn_ok(bn_mean, bn_invstd, bn_gamma, bn_beta)))
+  if (c.path == kPwStream && (!bn_mean || bn_ok(bn_mean, bn_invstd, bn_gamma, bn_beta)))
     // K = C = 64 / 128: the persistent streaming kernel (pw_stream.hip), bit-identical outputs
-  {
-    FoldTail ft;
-    if (stats) fold_take(stats, pw_stream_fwd_rows(N * OH * OW, K), K, 1, &ft);
-    return fold_status(pw_stream_fwd(x, N, H, W, stride, OH, OW, w_kc, K, bias, y, bn_mean, bn_invstd, bn_gamma,
-                                     bn_beta, bn_relu, stats, as_stream(stream), stats ? &ft : nullptr),
-                       stats ? ft : FoldTail{});
-  }
+    return pw_fold_launch(stats, c.plan, K, [&](const FoldTail* ft) {
+      return pw_stream_fwd(x, N, H, W, stride, OH, OW, w_kc, K, bias, y, bn_mean, bn_invstd, bn_gamma, bn_beta,
+                           bn_relu, stats, c.plan, as_stream(stream), ft);
+    });
   return conv_fwd_ex(img1(x, N, H, W, C, OH, OW, stride, N * OH * OW), w_kc, K, C, bias, y, bn_mean,
                      bn_invstd, bn_gamma, bn_beta, bn_relu, stats, stream);
 }
@@ -83,9 +97,11 @@ DK_API int dk_pwconv_dgrad_f32(const float* dy, int N, int OH, int OW, int K, co
   MatDesc b = mat(w_kc, K, C, C);
   const hipStream_t st = as_stream(stream);
   const bool vec = vec_ok(a, K, 4) && vec_ok(b, 4, C);
-  if (stride == 1 && vec && aligned16(dy) && aligned16(w_kc) && aligned16(dx) && pw_deep_dgrad_ok(K, C, M))
+  if (stride == 1 && vec && aligned16(dy) && aligned16(w_kc) && aligned16(dx)) {
     // the deep dgrad kernel's plain form (pw_deep.hip): bit-identical dx (the skip projections)
-    return pw_deep_dgrad_plain(dy, M, K, C, w_kc, dx, st);
+    const PwPlan deep = pw_deep_dgrad_plan(M, K, C);
+    if (deep.rows) return pw_deep_dgrad_plain(dy, M, K, C, w_kc, dx, deep, st);
+  }
   if (stride == 1) {
     EpStore ep = ep_store(dx, C, nullptr);
     if (vec) return igemm_rows<LdMatKC, MatDesc, LdMatIC, MatDesc, EpStore>(a, b, ep, M, C, K, st);
@@ -99,9 +115,8 @@ DK_API int dk_pwconv_dgrad_f32(const float* dy, int N, int OH, int OW, int K, co
 DK_API int dk_pwconv_dgrad_stats_rows(int N, int OH, int OW, int K, int C) { return stats_rows(N * OH * OW, C, K); }
 DK_API int dk_pwconv_dgrad_bnbwd_stats_rows(int N, int OH, int OW, int K, int C) {
   const int M = N * OH * OW;
-  if (pw_deep_dgrad_ok(K, C, M)) return pw_deep_dgrad_rows(M, K, C);
-  if (pw_stream_dgrad_ok(K, C, M)) return pw_stream_dgrad_rows(M);
-  return stats_rows(M, C, K, kRowBnBwd);
+  const PwChoice c = pw_dgrad_choice(M, K, C);
+  return c.path == kPwTiled ? stats_rows(M, C, K, kRowBnBwd) : c.plan.rows;
 }
 
 // dgrad + the BN-backward partial sums of the BatchNorm whose output this layer consumed
@@ -203,26 +218,21 @@ DK_API int dk_pwconv_dgrad_bnbwd_f32(const float* g, const float* bn_x, int N, i
   if (!vec_ok(b, 4, C) || K % 4 || !aligned16(g) || !aligned16(bn_x) || (dy_out && !aligned16(dy_out)) ||
       (size_t)K * 32 > 64 * 1024)
     return DK_ERR_ARGS;
-  if (pw_deep_dgrad_ok(K, C, M)) {
-    // the deep streaming kernel (pw_deep.hip): bit-identical dy and dx, its own partial rows
-    // (sized by dk_pwconv_dgrad_bnbwd_stats_rows: no other path may take this call)
+  const PwChoice c = pw_dgrad_choice(M, K, C);
+  if (c.path != kPwTiled) {
+    // the deep streaming kernel (pw_deep.hip) or, at K = C = 64, the persistent streaming kernel
+    // (pw_stream.hip): bit-identical dy and dx, their own partial rows (sized by
+    // dk_pwconv_dgrad_bnbwd_stats_rows: no other path may take this call)
     if (part && !bn_ok(bn_mean, bn_invstd, bn_gamma, bn_beta)) return DK_ERR_ARGS;
-    FoldTail ft;
-    if (part) fold_take(part, pw_deep_dgrad_rows(M, K, C), C, pw_deep_dgrad_slices(M, K, C), &ft);
-    return fold_status(pw_deep_dgrad_bnbwd(g, bn_x, M, K, C, out_mean, out_invstd, out_gamma, out_beta, out_relu, k12,
-                                           dy_out, w_kc, dx, residual, part ? x : nullptr, bn_mean, bn_invstd,
-                                           bn_gamma, bn_beta, bn_relu, part, st, part ? &ft : nullptr),
-                       part ? ft : FoldTail{});
-  }
-  if (pw_stream_dgrad_ok(K, C, M)) {
-    // K = C = 64: the persistent streaming kernel (pw_stream.hip), bit-identical results
-    if (part && !bn_ok(bn_mean, bn_invstd, bn_gamma, bn_beta)) return DK_ERR_ARGS;
-    FoldTail ft;
-    if (part) fold_take(part, pw_stream_dgrad_rows(M), C, 1, &ft);
-    return fold_status(pw_stream_dgrad_bnbwd(g, bn_x, M, out_mean, out_invstd, out_gamma, out_beta, out_relu, k12,
-                                             dy_out, w_kc, dx, residual, part ? x : nullptr, bn_mean, bn_invstd,
-                                             bn_gamma, bn_beta, bn_relu, part, st, part ? &ft : nullptr),
-                       part ? ft : FoldTail{});
+    return pw_fold_launch(part, c.plan, C, [&](const FoldTail* ft) {
+      if (c.path == kPwDeep)
+        return pw_deep_dgrad_bnbwd(g, bn_x, M, K, C, out_mean, out_invstd, out_gamma, out_beta, out_relu, k12, dy_out,
+                                   w_kc, dx, residual, part ? x : nullptr, bn_mean, bn_invstd, bn_gamma, bn_beta,
+                                   bn_relu, part, c.plan, st, ft);
+      return pw_stream_dgrad_bnbwd(g, bn_x, M, out_mean, out_invstd, out_gamma, out_beta, out_relu, k12, dy_out, w_kc,
+                                   dx, residual, part ? x : nullptr, bn_mean, bn_invstd, bn_gamma, bn_beta, bn_relu,
+                                   part, c.plan, st, ft);
+    });
   }
   if (!part) {
     EpStore ep = ep_store(dx, C, nullptr, residual);

@@ -30,8 +30,8 @@
 
 #include <atomic>
 
-#include "dk_common.h"
 #include "fold_tail.h"
+#include "pw_launch.h"
 
 namespace dk {
 
@@ -307,19 +307,28 @@ static int pwf_blocks(long long P, int K, int C, int* tpb_out) {
   return (int)((ntiles + tpb - 1) / tpb);
 }
 
-int splitk_reduce(const float* ws, int splits, int M, int N, float* out, const float* w, float l2, int mode, int C,
-                  int Cp, int R, int S, hipStream_t st);
-
 }  // namespace dk
 
 using namespace dk;
+
+// The path of the fused backward (dk_pwconv_bwd_fused_rows / _preferred / _workspace_bytes,
+// dk_pwconv_bwd_bnbwd_f32, dk_pwconv_bwd_bnbwd_lattice_f32): the streaming kernel (pw_stream.hip) at
+// K = C = 64, the weight-stationary deep kernel (pw_deep.hip) at K in {128, 256}, else this file's
+// tiled kernel (rows: pwf_blocks).  P: the pixel count, already held within int.
+//
+// Launch-only conditions (what the queries cannot see; DESIGN.md lists them): none re-routes a call.
+// The deep kernel takes an input BatchNorm only with its partials and the streaming kernel partials
+// only with an input BatchNorm: both refuse the other combination instead of falling to another path.
+static PwChoice pw_bwd_choice(long long P, int K, int C) {
+  return pw_choice(pw_deep_bwd_plan((int)P, K, C), pw_stream_bwd_plan((int)P, K, C));
+}
 
 DK_API int dk_pwconv_bwd_fused_rows(int N, int OH, int OW, int K, int C) {
   if (N < 1 || OH < 1 || OW < 1) return 0;
   const long long P = (long long)N * OH * OW;
   if (P >= (1ll << 31)) return 0;
-  if (pw_stream_bwd_ok(K, C, (int)P)) return pw_stream_bwd_rows((int)P);
-  if (pw_deep_bwd_ok(K, C, (int)P)) return pw_deep_bwd_rows((int)P, K, C);
+  const PwChoice c = pw_bwd_choice(P, K, C);
+  if (c.path != kPwTiled) return c.plan.rows;
   if (!pwf_supported(K, C)) return 0;
   return pwf_blocks(P, K, C, nullptr);
 }
@@ -329,8 +338,7 @@ DK_API int dk_pwconv_bwd_fused_rows(int N, int OH, int OW, int K, int C) {
 // the layers use it by default there.
 DK_API int dk_pwconv_bwd_fused_preferred(int N, int OH, int OW, int K, int C) {
   if (N < 1 || OH < 1 || OW < 1 || (long long)N * OH * OW >= (1ll << 31)) return 0;
-  const int P = N * OH * OW;
-  return (pw_stream_bwd_ok(K, C, P) || pw_deep_bwd_ok(K, C, P)) ? 1 : 0;
+  return pw_bwd_choice((long long)N * OH * OW, K, C).path != kPwTiled ? 1 : 0;
 }
 
 DK_API size_t dk_pwconv_bwd_fused_workspace_bytes(int N, int OH, int OW, int K, int C) {
@@ -354,23 +362,21 @@ DK_API int dk_pwconv_bwd_bnbwd_lattice_f32(const float* g, const float* bn_x, in
   if (N < 1 || OH < 1 || OW < 1 || stride < 2 || H < (OH - 1) * stride + 1 || W < (OW - 1) * stride + 1)
     return DK_ERR_ARGS;
   const long long P = (long long)N * OH * OW;
-  if (!pw_stream_bwd_ok(K, C, (int)P) || (long long)N * H * W * C * 4 >= (1ll << 31)) return DK_ERR_ARGS;
+  const PwChoice c = pw_bwd_choice(P, K, C);
+  if (c.path != kPwStream || (long long)N * H * W * C * 4 >= (1ll << 31)) return DK_ERR_ARGS;
   if (!g || !bn_x || !x || !w_kc || !dw_kc || !dx || !out_mean || !out_invstd || !out_gamma || !out_beta || !k12 ||
       !bn_mean || !bn_invstd || !bn_gamma || !bn_beta)
     return DK_ERR_ARGS;
   auto al = [](const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; };
   if (!al(g) || !al(bn_x) || !al(x) || !al(dx) || !al(ws)) return DK_ERR_ARGS;
-  const int nb = pw_stream_bwd_rows((int)P);
-  if (ws_bytes < (size_t)nb * K * C * sizeof(float)) return DK_ERR_WORKSPACE;
+  if (ws_bytes < (size_t)c.plan.rows * K * C * sizeof(float)) return DK_ERR_WORKSPACE;
   float* wp = static_cast<float*>(ws);
-  FoldTail ft;
-  if (part) fold_take(part, nb, C, 1, &ft);
   const int lat[5] = {stride, H, W, OH, OW};
-  int rc = pw_stream_bwd_fused(g, bn_x, (int)P, out_mean, out_invstd, out_gamma, out_beta, out_relu, k12, w_kc, dx,
+  return pw_bwd_fold_launch(part, c.plan, K, C, wp, w_kc, l2, dw_kc, st, [&](const FoldTail* ft) {
+    return pw_stream_bwd_fused(g, bn_x, (int)P, out_mean, out_invstd, out_gamma, out_beta, out_relu, k12, w_kc, dx,
                                nullptr, x, part ? bn_mean : nullptr, bn_invstd, bn_gamma, bn_beta, bn_relu, part,
-                               bn_mean, bn_invstd, bn_gamma, bn_beta, bn_relu, wp, st, part ? &ft : nullptr, lat);
-  if (rc) return rc;
-  return fold_status(wgrad_reduce(wp, nb, K, C, dw_kc, l2 != 0.f ? w_kc : nullptr, l2, st), part ? ft : FoldTail{});
+                               bn_mean, bn_invstd, bn_gamma, bn_beta, bn_relu, wp, c.plan, st, ft, lat);
+  });
 }
 
 DK_API int dk_pwconv_bwd_bnbwd_f32(const float* g, const float* bn_x, int N, int OH, int OW, int K,
@@ -384,7 +390,8 @@ DK_API int dk_pwconv_bwd_bnbwd_f32(const float* g, const float* bn_x, int N, int
   if (N < 1 || OH < 1 || OW < 1 || (long long)N * OH * OW >= (1ll << 31)) return DK_ERR_ARGS;
   // the deep kernel takes an input BN only with its partials (the rows / workspace queries assume the
   // deep kernel whenever its shape fits, so that combination is refused rather than re-routed)
-  const bool deep = pw_deep_bwd_ok(K, C, N * OH * OW);
+  const PwChoice c = pw_bwd_choice((long long)N * OH * OW, K, C);
+  const bool deep = c.path == kPwDeep;
   if (deep && (bn_mean != nullptr) != (part != nullptr)) return DK_ERR_ARGS;
   if (!pwf_supported(K, C) && !deep) return DK_ERR_ARGS;
   if (!g || !bn_x || !x || !w_kc || !dw_kc || !dx || !out_mean || !out_invstd || !out_gamma || !out_beta || !k12)
@@ -397,33 +404,20 @@ DK_API int dk_pwconv_bwd_bnbwd_f32(const float* g, const float* bn_x, int N, int
   if (!al(g) || !al(bn_x) || !al(x) || !al(out_mean) || !al(out_invstd) || !al(out_gamma) || !al(out_beta) ||
       !al(k12) || !al(ws))
     return DK_ERR_ARGS;
-  if (pw_stream_bwd_ok(K, C, (int)P)) {
-    // K = C = 64: the persistent streaming kernel (pw_stream.hip)
-    const int nb = pw_stream_bwd_rows((int)P);
-    if (ws_bytes < (size_t)nb * K * C * sizeof(float)) return DK_ERR_WORKSPACE;
+  if (c.path != kPwTiled) {
+    // K = C = 64: the persistent streaming kernel (pw_stream.hip); K in {128, 256}: the weight-stationary
+    // fused kernel (pw_deep.hip)
+    if (ws_bytes < (size_t)c.plan.rows * K * C * sizeof(float)) return DK_ERR_WORKSPACE;
     float* wp = static_cast<float*>(ws);
-    FoldTail ft;
-    if (part) fold_take(part, nb, C, 1, &ft);
-    int rc = pw_stream_bwd_fused(g, bn_x, (int)P, out_mean, out_invstd, out_gamma, out_beta, out_relu, k12, w_kc, dx,
-                                 residual, x, bn_mean, bn_invstd, bn_gamma, bn_beta, bn_relu, part, bn_mean,
-                                 bn_invstd, bn_gamma, bn_beta, bn_relu, wp, st, part ? &ft : nullptr);
-    if (rc) return rc;
-    return fold_status(wgrad_reduce(wp, nb, K, C, dw_kc, l2 != 0.f ? w_kc : nullptr, l2, st),
-                       part ? ft : FoldTail{});
-  }
-  if (deep) {
-    // K in {128, 256}: the weight-stationary fused kernel (pw_deep.hip)
-    const int nb = pw_deep_bwd_rows((int)P, K, C);
-    if (ws_bytes < (size_t)nb * K * C * sizeof(float)) return DK_ERR_WORKSPACE;
-    float* wp = static_cast<float*>(ws);
-    FoldTail ft;
-    if (part) fold_take(part, nb, C, pw_deep_bwd_slices((int)P, K, C), &ft);
-    int rc = pw_deep_bwd_bnbwd(g, bn_x, (int)P, K, C, out_mean, out_invstd, out_gamma, out_beta, out_relu, k12, w_kc,
-                               dx, residual, x, bn_mean, bn_invstd, bn_gamma, bn_beta, bn_relu, part, wp, st,
-                               part ? &ft : nullptr);
-    if (rc) return rc;
-    return fold_status(wgrad_reduce(wp, nb, K, C, dw_kc, l2 != 0.f ? w_kc : nullptr, l2, st),
-                       part ? ft : FoldTail{});
+    return pw_bwd_fold_launch(part, c.plan, K, C, wp, w_kc, l2, dw_kc, st, [&](const FoldTail* ft) {
+      if (deep)
+        return pw_deep_bwd_bnbwd(g, bn_x, (int)P, K, C, out_mean, out_invstd, out_gamma, out_beta, out_relu, k12, w_kc,
+                                 dx, residual, x, bn_mean, bn_invstd, bn_gamma, bn_beta, bn_relu, part, wp, c.plan, st,
+                                 ft);
+      return pw_stream_bwd_fused(g, bn_x, (int)P, out_mean, out_invstd, out_gamma, out_beta, out_relu, k12, w_kc, dx,
+                                 residual, x, bn_mean, bn_invstd, bn_gamma, bn_beta, bn_relu, part, bn_mean, bn_invstd,
+                                 bn_gamma, bn_beta, bn_relu, wp, c.plan, st, ft);
+    });
   }
   int tpb = 1;
   const int nblk = pwf_blocks(P, K, C, &tpb);

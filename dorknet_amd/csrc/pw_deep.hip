@@ -25,11 +25,8 @@
 // MFMA k order 8q + 4h + e (h = lane half), as the tiled engine: outputs are bit-identical to it.
 #include <stdlib.h>
 
-#include <algorithm>
-#include <atomic>
-
-#include "dk_common.h"
 #include "fold_tail.h"
+#include "pw_launch.h"
 
 // Timing experiments only (scripts/pwd_exp.sh builds variant libraries; 0 in the product build):
 // bit 0 drops the epilogue stores, bit 1 the on-load transforms, bit 3 the weight loads.
@@ -1097,322 +1094,150 @@ __global__ __launch_bounds__(NT16, 2) void bwd16_kernel(BwdArgs a) {
 }
 
 // ---------------------------------------------------------------------------------------
-// Host side: the instantiated reductions and the grid.
+// Host side: the instantiated families (pw_launch.h), one plan per operation, the launchers.
 // ---------------------------------------------------------------------------------------
-#define DK_PWD_KR(X) X(64) X(128) X(256) X(512)
-#define DK_PWD_KR_DGRAD(X) X(64) X(128) X(256)  // (K = 512: dgrad16_kernel)
-
-static int occupancy(const void* fn, int nt = NT) {
-  int v = 0;
-  if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&v, fn, nt, 0) != hipSuccess || v < 1) v = 1;
-  return v;
-}
-
+// fwd_kernel's forms at reduction KR: index 8 BN + 4 STATS + 2 STRIDED + HB.
 template <int KR>
-static int fwd_occ() {
-  static const int occ = [] {
-#define DK_F(B_, S_, T_) reinterpret_cast<const void*>(&fwd_kernel<KR, B_, S_, T_, false>), \
-                         reinterpret_cast<const void*>(&fwd_kernel<KR, B_, S_, T_, true>)
-    const void* fs[] = {DK_F(true, true, false), DK_F(true, false, false), DK_F(false, true, false),
-                        DK_F(false, false, false), DK_F(true, true, true), DK_F(true, false, true),
-                        DK_F(false, true, true), DK_F(false, false, true)};
-#undef DK_F
-    int o = 1 << 20;
-    for (const void* f : fs) o = std::min(o, occupancy(f));
-    return o;
-  }();
-  return occ;
+static const PwKernelTable<16, FwdArgs>& fwd_forms() {
+  static const auto t = pw_table(PwKernelTable<16, FwdArgs>{{DK_PW_F4(fwd_kernel, KR)}, NT, 0xFFFFu});
+  return t;
 }
+// dgrad_kernel's / dgrad16_kernel's forms: index 2 RES + PART, then PLAIN.
+// PLAIN (form 4) is not counted: it writes no partial rows, so nothing is sized from its own grid; it
+// runs on the grid of the four fused forms, and counting it could only lower that grid, which sets
+// their row counts and summation order.
 template <int KR>
-static int dgrad_occ() {
-  static const int occ = [] {
-    const void* fs[] = {reinterpret_cast<const void*>(&dgrad_kernel<KR, true, true>),
-                        reinterpret_cast<const void*>(&dgrad_kernel<KR, true, false>),
-                        reinterpret_cast<const void*>(&dgrad_kernel<KR, false, true>),
-                        reinterpret_cast<const void*>(&dgrad_kernel<KR, false, false>)};
-    int o = 1 << 20;
-    for (const void* f : fs) o = std::min(o, occupancy(f));
-    return o;
-  }();
-  return occ;
+static const PwKernelTable<5, DgradArgs>& dgrad_forms() {
+  static const auto t = pw_table(PwKernelTable<5, DgradArgs>{
+      {DK_PW_F2(dgrad_kernel, KR), &dgrad_kernel<KR, false, false, true>}, NT, 0x0Fu});
+  return t;
+}
+static const PwKernelTable<5, DgradArgs>& dgrad16_forms() {
+  static const auto t = pw_table(PwKernelTable<5, DgradArgs>{
+      {DK_PW_F2(dgrad16_kernel, 512), &dgrad16_kernel<512, false, false, true>}, NT16, 0x0Fu});
+  return t;
+}
+// bwd_kernel's / bwd16_kernel's forms: index 2 RES + BNIN.
+static const PwKernelTable<4, BwdArgs>& bwd_forms() {
+  static const auto t = pw_table(PwKernelTable<4, BwdArgs>{{DK_PW_F2(bwd_kernel, 128)}, NT, 0xFu});
+  return t;
+}
+static const PwKernelTable<4, BwdArgs>& bwd16_forms() {
+  static const auto t = pw_table(PwKernelTable<4, BwdArgs>{{DK_PW_F2(bwd16_kernel, 256)}, NT16, 0xFu});
+  return t;
 }
 
-template <int KR>
-static int dgrad16_occ() {
-  static const int occ = [] {
-    const void* fs[] = {reinterpret_cast<const void*>(&dgrad16_kernel<KR, true, true>),
-                        reinterpret_cast<const void*>(&dgrad16_kernel<KR, true, false>),
-                        reinterpret_cast<const void*>(&dgrad16_kernel<KR, false, true>),
-                        reinterpret_cast<const void*>(&dgrad16_kernel<KR, false, false>)};
-    int o = 1 << 20;
-    for (const void* f : fs) o = std::min(o, occupancy(f, NT16));
-    return o;
-  }();
-  return occ;
+// The family of a reduction length (nullptr: not instantiated).
+static const PwKernelTable<16, FwdArgs>* fwd_family(int C) {
+  return C == 64 ? &fwd_forms<64>() : C == 128 ? &fwd_forms<128>() : C == 256 ? &fwd_forms<256>()
+       : C == 512 ? &fwd_forms<512>() : nullptr;
 }
-
-template <int KR>
-static int bwd16_occ() {
-  static const int occ = [] {
-    const void* fs[] = {reinterpret_cast<const void*>(&bwd16_kernel<KR, true, true>),
-                        reinterpret_cast<const void*>(&bwd16_kernel<KR, true, false>),
-                        reinterpret_cast<const void*>(&bwd16_kernel<KR, false, true>),
-                        reinterpret_cast<const void*>(&bwd16_kernel<KR, false, false>)};
-    int o = 1 << 20;
-    for (const void* f : fs) o = std::min(o, occupancy(f, NT16));
-    return o;
-  }();
-  return occ;
+// K = 512 runs the two-waves-per-SIMD 16 x 16 kernel (dgrad16_kernel): 16-pixel tiles, NT16 threads.
+static const PwKernelTable<5, DgradArgs>* dgrad_family(int K) {
+  return K == 64 ? &dgrad_forms<64>() : K == 128 ? &dgrad_forms<128>() : K == 256 ? &dgrad_forms<256>()
+       : K == 512 ? &dgrad16_forms() : nullptr;
 }
-
-template <int KR>
-static int bwd_occ() {
-  static const int occ = [] {
-    const void* fs[] = {reinterpret_cast<const void*>(&bwd_kernel<KR, true, true>),
-                        reinterpret_cast<const void*>(&bwd_kernel<KR, true, false>),
-                        reinterpret_cast<const void*>(&bwd_kernel<KR, false, true>),
-                        reinterpret_cast<const void*>(&bwd_kernel<KR, false, false>)};
-    int o = 1 << 20;
-    for (const void* f : fs) o = std::min(o, occupancy(f));
-    return o;
-  }();
-  return occ;
+// K = 256 runs the two-waves-per-SIMD 16 x 16 kernel (bwd16_kernel), 16-pixel tiles.  At K = 128 the
+// 16 x 16 layout (four waves per SIMD) measured slower than bwd_kernel<128> (173.6 vs 163.0 us at
+// 28 x 28 x 128, profiles/r06f_pwd16_bwd_ab.txt), so bwd16_kernel is instantiated at K = 256 only.
+static const PwKernelTable<4, BwdArgs>* bwd_family(int K) {
+  return K == 128 ? &bwd_forms() : K == 256 ? &bwd16_forms() : nullptr;
 }
-
-// Row-tile walkers per column group: every resident slot once (all blocks of a CU run at the same
-// time, so each CU gets the same number of blocks and each block within one tile of the same share),
-// at most one walker per tile; a multiple of the 8 XCDs when that costs no extra tile per walker, so
-// that walker x of every column group runs on one XCD (block id x + gx * y) and the groups of a row
-// tile share that XCD's L2 copy of its pixels.  A function of (M, N, occupancy) only: callers
-// allocate exactly the partial rows the launch writes.
-static int grid_x(int M, int N, int occ, int tr = TR) {
-  const int ntiles = (M + tr - 1) / tr;
-  const int groups = N < NB ? 1 : N / NB;  // (N < NB: the C = 64 fused backward, one column group)
-  int slots = occ * 256 / groups;
-  if (slots < 1) slots = 1;
-  int gx = std::min(ntiles, slots);
-  const int g8 = gx / 8 * 8;
-  if (g8 >= 8 && (ntiles + g8 - 1) / g8 == (ntiles + gx - 1) / gx) gx = g8;
-  return gx;
-}
+// Pixels per tile of a family: the 8-wave blocks walk 16-pixel tiles.
+static int tile_rows(int threads) { return threads == NT16 ? TR16 : TR; }
 
 }  // namespace pwd
 
 // Knob 11 = 0 (or the streaming knob 3 = 0) keeps the earlier paths.
 static bool pwd_enabled() { return knob(kKnobPwDeep) == 1 && pw_stream_enabled(); }
+// The fused deep backward: default on; knob 14 = 0 keeps the dgrad + side-stream weight gradient pair.
+static bool pwd_bwd_enabled() { return knob(kKnobPwDeepBwd) == 1 && pwd_enabled(); }
 
-static bool pwd_kr(int KR) { return KR == 64 || KR == 128 || KR == 256 || KR == 512; }
-
-// The shapes the deep kernels take: reduction KR in {64, 128, 256, 512} with at least 128 channels
-// on one side (K = C = 64 stays on pw_stream.hip), outputs a multiple of the block's 128 columns.
-bool pw_deep_fwd_ok(int K, int C, int M, size_t xbytes) {
-  if (!pwd_enabled() || M <= 0 || (K < 128 && C < 128) || !pwd_kr(C) || K % pwd::NB) return false;
-  return xbytes < ((size_t)1 << 31) && (size_t)M * K * 4 < ((size_t)1 << 31);
+// The shapes the deep kernels take: reduction in {64, 128, 256, 512} with at least 128 channels on
+// one side (K = C = 64 stays on pw_stream.hip), outputs a multiple of the block's 128 columns.  One
+// partial row per row-tile walker, one channel slice per column group.
+PwPlan pw_deep_fwd_plan(int M, int K, int C, size_t xbytes) {
+  if (!pwd_enabled() || M <= 0 || (K < 128 && C < 128) || K % pwd::NB) return {0, 0};
+  if (xbytes >= ((size_t)1 << 31) || (size_t)M * K * 4 >= ((size_t)1 << 31)) return {0, 0};
+  const auto* t = pwd::fwd_family(C);
+  if (!t) return {0, 0};
+  return {pw_deep_grid(M, K, pwd::NB, pwd::TR, t->occ), K / pwd::NB};
 }
-bool pw_deep_dgrad_ok(int K, int C, int M) {
-  if (!pwd_enabled() || M <= 0 || (K < 128 && C < 128) || !pwd_kr(K) || C % pwd::NB) return false;
-  return (size_t)M * (K > C ? K : C) * 4 < ((size_t)1 << 31);
+PwPlan pw_deep_dgrad_plan(int M, int K, int C) {
+  if (!pwd_enabled() || M <= 0 || (K < 128 && C < 128) || C % pwd::NB) return {0, 0};
+  if ((size_t)M * (K > C ? K : C) * 4 >= ((size_t)1 << 31)) return {0, 0};
+  const auto* t = pwd::dgrad_family(K);
+  if (!t) return {0, 0};
+  return {pw_deep_grid(M, C, pwd::NB, pwd::tile_rows(t->threads), t->occ), C / pwd::NB};
 }
-
-int pw_deep_fwd_rows(int M, int K, int C) {
-#define DK_ROWS(kr) \
-  if (C == kr) return pwd::grid_x(M, K, pwd::fwd_occ<kr>());
-  DK_PWD_KR(DK_ROWS)
-#undef DK_ROWS
-  return 0;
+// Fused deep backward (bwd_kernel): reduction K in {128, 256}, C a multiple of the block's 128 columns,
+// or K = 128 with C = 64 (one column group, half its waves staging only: the downsampling blocks' first
+// pointwise layer at 28 x 28, whose unfused pair stored dy and re-read it on the side stream).
+PwPlan pw_deep_bwd_plan(int M, int K, int C) {
+  if (!pwd_bwd_enabled() || M <= 0 || (C % pwd::NB && !(K == 128 && C == 64))) return {0, 0};
+  if ((size_t)M * (K > C ? K : C) * 4 >= ((size_t)1 << 31)) return {0, 0};
+  const auto* t = pwd::bwd_family(K);
+  if (!t) return {0, 0};
+  return {pw_deep_grid(M, C, pwd::NB, pwd::tile_rows(t->threads), t->occ), C < pwd::NB ? 1 : C / pwd::NB};
 }
-int pw_deep_fwd_slices(int M, int K, int C) { return K / pwd::NB; }
-// K = 512 runs the two-waves-per-SIMD 16 x 16 kernel (dgrad16_kernel), 16-pixel tiles.
-static bool pwd_dgrad16(int K) { return K == 512; }
-
-int pw_deep_dgrad_rows(int M, int K, int C) {
-  if (pwd_dgrad16(K)) return pwd::grid_x(M, C, pwd::dgrad16_occ<512>(), pwd::TR16);
-#define DK_ROWS(kr) \
-  if (K == kr) return pwd::grid_x(M, C, pwd::dgrad_occ<kr>());
-  DK_PWD_KR_DGRAD(DK_ROWS)
-#undef DK_ROWS
-  return 0;
-}
-int pw_deep_dgrad_slices(int M, int K, int C) { return C / pwd::NB; }
 
 int pw_deep_fwd(const float* x, int N, int H, int W, int stride, int OH, int OW, const float* w, int K, int C,
                 const float* bias, float* y, const float* im, const float* iis, const float* ig, const float* ib,
-                int irelu, double* part, hipStream_t st, const FoldTail* ft) {
+                int irelu, double* part, PwPlan plan, hipStream_t st, const FoldTail* ft) {
+  const auto* t = pwd::fwd_family(C);
+  if (!t || plan.rows == 0) return DK_ERR_ARGS;
   const int M = N * OH * OW;
   const bool strided = stride != 1 || H != OH || W != OW;
   pwd::FwdArgs a{x, w, bias, y, im, iis, ig, ib, irelu, part, M, K, H, W, OH, OW, stride,
                  (uint32_t)((size_t)N * H * W * C * 4)};
   if (ft && part) a.ft = *ft;
   a.nt = nt_stores(kNtPwd);
-  const dim3 grid(pw_deep_fwd_rows(M, K, C), K / pwd::NB);
-  if (grid.x == 0) return DK_ERR_ARGS;
-#define DK_L(kr, B_, S_, T_)                                                                          \
-  do {                                                                                                \
-    if (bias)                                                                                         \
-      hipLaunchKernelGGL((pwd::fwd_kernel<kr, B_, S_, T_, true>), grid, dim3(pwd::NT), 0, st, a);     \
-    else                                                                                              \
-      hipLaunchKernelGGL((pwd::fwd_kernel<kr, B_, S_, T_, false>), grid, dim3(pwd::NT), 0, st, a);    \
-  } while (0)
-#define DK_FWD(kr)                    \
-  if (C == kr) {                      \
-    if (strided) {                    \
-      if (im && part)                 \
-        DK_L(kr, true, true, true);   \
-      else if (im)                    \
-        DK_L(kr, true, false, true);  \
-      else if (part)                  \
-        DK_L(kr, false, true, true);  \
-      else                            \
-        DK_L(kr, false, false, true); \
-    } else if (im && part)            \
-      DK_L(kr, true, true, false);    \
-    else if (im)                      \
-      DK_L(kr, true, false, false);   \
-    else if (part)                    \
-      DK_L(kr, false, true, false);   \
-    else                              \
-      DK_L(kr, false, false, false);  \
-    return launch_status();           \
-  }
-  DK_PWD_KR(DK_FWD)
-#undef DK_FWD
-#undef DK_L
-  return DK_ERR_ARGS;
+  t->launch(8 * (im != nullptr) + 4 * (part != nullptr) + 2 * strided + (bias != nullptr), dim3(plan.rows, plan.slices),
+            st, a);
+  return launch_status();
 }
 
 int pw_deep_dgrad_bnbwd(const float* g, const float* bn_x, int M, int K, int C, const float* om, const float* ois,
                         const float* og, const float* ob, int orelu, const float* k12, float* dy_out, const float* w,
                         float* dx, const float* res, const float* x, const float* im, const float* iis,
-                        const float* ig, const float* ib, int irelu, double* part, hipStream_t st,
+                        const float* ig, const float* ib, int irelu, double* part, PwPlan plan, hipStream_t st,
                         const FoldTail* ft) {
+  const auto* t = pwd::dgrad_family(K);
+  if (!t || plan.rows == 0) return DK_ERR_ARGS;
   pwd::DgradArgs a{g, bn_x, dy_out, w, dx, res, x, om, ois, og, ob, k12, orelu, im, iis, ig, ib, irelu, part, M, C};
   if (ft && part) a.ft = *ft;
   a.nt = nt_stores(kNtPwd);
-  const dim3 grid(pw_deep_dgrad_rows(M, K, C), C / pwd::NB);
-  if (grid.x == 0) return DK_ERR_ARGS;
-  if (pwd_dgrad16(K)) {
-#define DK_L16(R_, P_) hipLaunchKernelGGL((pwd::dgrad16_kernel<512, R_, P_>), grid, dim3(pwd::NT16), 0, st, a)
-    if (res && x)
-      DK_L16(true, true);
-    else if (res)
-      DK_L16(true, false);
-    else if (x)
-      DK_L16(false, true);
-    else
-      DK_L16(false, false);
-#undef DK_L16
-    return launch_status();
-  }
-#define DK_L(kr, R_, P_) hipLaunchKernelGGL((pwd::dgrad_kernel<kr, R_, P_>), grid, dim3(pwd::NT), 0, st, a)
-#define DK_DG(kr)             \
-  if (K == kr) {              \
-    if (res && x)             \
-      DK_L(kr, true, true);   \
-    else if (res)             \
-      DK_L(kr, true, false);  \
-    else if (x)               \
-      DK_L(kr, false, true);  \
-    else                      \
-      DK_L(kr, false, false); \
-    return launch_status();   \
-  }
-  DK_PWD_KR_DGRAD(DK_DG)
-#undef DK_DG
-#undef DK_L
-  return DK_ERR_ARGS;
+  t->launch(2 * (res != nullptr) + (x != nullptr), dim3(plan.rows, plan.slices), st, a);
+  return launch_status();
 }
 
 // The plain deep dgrad (PLAIN: dy given, no BatchNorm around it): dx[M][C] = dy . W, bit-identical to the
 // tiled engine's (same MFMA k order).  The downsampling blocks' skip projections at stride 1 into the
-// compact lattice.
-int pw_deep_dgrad_plain(const float* dy, int M, int K, int C, const float* w, float* dx, hipStream_t st) {
+// compact lattice.  plan: pw_deep_dgrad_plan's.
+int pw_deep_dgrad_plain(const float* dy, int M, int K, int C, const float* w, float* dx, PwPlan plan,
+                        hipStream_t st) {
+  const auto* t = pwd::dgrad_family(K);
+  if (!t || plan.rows == 0) return DK_ERR_ARGS;
   pwd::DgradArgs a{dy, nullptr, nullptr, w, dx, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, 0,
                    nullptr, nullptr, nullptr, nullptr, 0, nullptr, M, C};
   a.nt = nt_stores(kNtPwd);
-  const dim3 grid(pw_deep_dgrad_rows(M, K, C), C / pwd::NB);
-  if (grid.x == 0) return DK_ERR_ARGS;
-  if (pwd_dgrad16(K)) {
-    hipLaunchKernelGGL((pwd::dgrad16_kernel<512, false, false, true>), grid, dim3(pwd::NT16), 0, st, a);
-    return launch_status();
-  }
-#define DK_DG(kr)                                                                                           \
-  if (K == kr) {                                                                                            \
-    hipLaunchKernelGGL((pwd::dgrad_kernel<kr, false, false, true>), grid, dim3(pwd::NT), 0, st, a);         \
-    return launch_status();                                                                                 \
-  }
-  DK_PWD_KR_DGRAD(DK_DG)
-#undef DK_DG
-  return DK_ERR_ARGS;
+  t->launch(4, dim3(plan.rows, plan.slices), st, a);
+  return launch_status();
 }
-
-// Fused deep backward (bwd_kernel): reduction K in {128, 256}, C a multiple of the block's 128 columns,
-// or K = 128 with C = 64 (one column group, half its waves staging only: the downsampling blocks' first
-// pointwise layer at 28 x 28, whose unfused pair stored dy and re-read it on the side stream).
-// Default on; knob 14 = 0 keeps the dgrad + side-stream weight gradient pair.
-static bool pwd_bwd_enabled() { return knob(kKnobPwDeepBwd) == 1 && pwd_enabled(); }
-bool pw_deep_bwd_ok(int K, int C, int M) {
-  if (!pwd_bwd_enabled() || M <= 0 || (K != 128 && K != 256) || (C % pwd::NB && !(K == 128 && C == 64)))
-    return false;
-  return (size_t)M * (K > C ? K : C) * 4 < ((size_t)1 << 31);
-}
-// K = 256 runs the two-waves-per-SIMD 16 x 16 kernel (bwd16_kernel), 16-pixel tiles.  At K = 128 the
-// 16 x 16 layout (four waves per SIMD) measured slower than bwd_kernel<128> (173.6 vs 163.0 us at
-// 28 x 28 x 128, profiles/r06f_pwd16_bwd_ab.txt), so bwd16_kernel is instantiated at K = 256 only.
-static bool pwd_bwd16(int K) { return K == 256; }
-
-int pw_deep_bwd_rows(int M, int K, int C) {
-  if (pwd_bwd16(K)) return pwd::grid_x(M, C, pwd::bwd16_occ<256>(), pwd::TR16);
-  if (K == 128) return pwd::grid_x(M, C, pwd::bwd_occ<128>());
-  return 0;
-}
-int pw_deep_bwd_slices(int M, int K, int C) { return C < pwd::NB ? 1 : C / pwd::NB; }
 
 int pw_deep_bwd_bnbwd(const float* g, const float* bn_x, int M, int K, int C, const float* om, const float* ois,
                       const float* og, const float* ob, int orelu, const float* k12, const float* w, float* dx,
                       const float* res, const float* x, const float* im, const float* iis, const float* ig,
-                      const float* ib, int irelu, double* part, float* wpart, hipStream_t st, const FoldTail* ft) {
+                      const float* ib, int irelu, double* part, float* wpart, PwPlan plan, hipStream_t st,
+                      const FoldTail* ft) {
   if ((im != nullptr) != (part != nullptr)) return DK_ERR_ARGS;
+  const auto* t = pwd::bwd_family(K);
+  if (!t || plan.rows == 0) return DK_ERR_ARGS;
   pwd::BwdArgs a{g, bn_x, w, dx, res, x, om, ois, og, ob, k12, orelu, im, iis, ig, ib, irelu, part, wpart, M, C};
   if (ft && part) a.ft = *ft;
   a.nt = nt_stores(kNtPwd);
-  const dim3 grid(pw_deep_bwd_rows(M, K, C), pw_deep_bwd_slices(M, K, C));
-  if (grid.x == 0) return DK_ERR_ARGS;
-  if (pwd_bwd16(K)) {
-#define DK_L16(kr, R_, B_) hipLaunchKernelGGL((pwd::bwd16_kernel<kr, R_, B_>), grid, dim3(pwd::NT16), 0, st, a)
-#define DK_B16(kr)             \
-  if (K == kr) {               \
-    if (res && im)             \
-      DK_L16(kr, true, true);  \
-    else if (res)              \
-      DK_L16(kr, true, false); \
-    else if (im)               \
-      DK_L16(kr, false, true); \
-    else                       \
-      DK_L16(kr, false, false); \
-    return launch_status();    \
-  }
-    DK_B16(256)
-#undef DK_B16
-#undef DK_L16
-  }
-#define DK_L(kr, R_, B_) hipLaunchKernelGGL((pwd::bwd_kernel<kr, R_, B_>), grid, dim3(pwd::NT), 0, st, a)
-#define DK_BW(kr)             \
-  if (K == kr) {              \
-    if (res && im)            \
-      DK_L(kr, true, true);   \
-    else if (res)             \
-      DK_L(kr, true, false);  \
-    else if (im)              \
-      DK_L(kr, false, true);  \
-    else                      \
-      DK_L(kr, false, false); \
-    return launch_status();   \
-  }
-  DK_BW(128)
-#undef DK_BW
-#undef DK_L
-  return DK_ERR_ARGS;
+  t->launch(2 * (res != nullptr) + (im != nullptr), dim3(plan.rows, plan.slices), st, a);
+  return launch_status();
 }
-
 
 }  // namespace dk

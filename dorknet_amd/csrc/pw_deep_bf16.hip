@@ -20,10 +20,8 @@
 // the same fp32 epilogue and RNE stores, statistics over the stored values (grouped per block).
 #include <stdlib.h>
 
-#include <algorithm>
-
-#include "dk_common.h"
 #include "fold_tail.h"
+#include "pw_launch.h"
 
 namespace dk {
 namespace pwd16 {
@@ -586,202 +584,112 @@ __global__ __launch_bounds__(NT, bwd_wps<KR>()) void bwd_kernel(DgradArgs a, flo
 }
 
 // ---------------------------------------------------------------------------------------
-// Host side
+// Host side: the instantiated families (pw_launch.h), one plan per operation, the launchers.
 // ---------------------------------------------------------------------------------------
-#define DK_PWD16_KR(X) X(128) X(256) X(512)
+// fwd_kernel's forms at reduction KR: index 4 BN + 2 STATS + HB.
+template <int KR>
+static const PwKernelTable<8, FwdArgs>& fwd_forms() {
+  static const auto t = pw_table(PwKernelTable<8, FwdArgs>{{DK_PW_F3(fwd_kernel, KR)}, NT, 0xFFu});
+  return t;
+}
+// dgrad_kernel's forms: index 2 RES + PART.
+template <int KR>
+static const PwKernelTable<4, DgradArgs>& dgrad_forms() {
+  static const auto t = pw_table(PwKernelTable<4, DgradArgs>{{DK_PW_F2(dgrad_kernel, KR)}, NT, 0xFu});
+  return t;
+}
+// bwd_kernel's forms: index 2 RES + BNIN.
+template <int KR>
+static const PwKernelTable<4, DgradArgs, float*>& bwd_forms() {
+  static const auto t = pw_table(PwKernelTable<4, DgradArgs, float*>{{DK_PW_F2(bwd_kernel, KR)}, NT, 0xFu});
+  return t;
+}
 
-static int occupancy(const void* fn) {
-  int v = 0;
-  if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&v, fn, NT, 0) != hipSuccess || v < 1) v = 1;
-  return v;
+// The family of a reduction length (nullptr: not instantiated).
+static const PwKernelTable<8, FwdArgs>* fwd_family(int C) {
+  return C == 128 ? &fwd_forms<128>() : C == 256 ? &fwd_forms<256>() : C == 512 ? &fwd_forms<512>() : nullptr;
 }
-template <int KR>
-static int fwd_occ() {
-  static const int occ = [] {
-#define DK_F(B_, S_) reinterpret_cast<const void*>(&fwd_kernel<KR, B_, S_, false>), \
-                     reinterpret_cast<const void*>(&fwd_kernel<KR, B_, S_, true>)
-    const void* fs[] = {DK_F(true, true), DK_F(true, false), DK_F(false, true), DK_F(false, false)};
-#undef DK_F
-    int o = 1 << 20;
-    for (const void* f : fs) o = std::min(o, occupancy(f));
-    return o;
-  }();
-  return occ;
+static const PwKernelTable<4, DgradArgs>* dgrad_family(int K) {
+  return K == 128 ? &dgrad_forms<128>() : K == 256 ? &dgrad_forms<256>() : K == 512 ? &dgrad_forms<512>() : nullptr;
 }
-template <int KR>
-static int dgrad_occ() {
-  static const int occ = [] {
-    const void* fs[] = {reinterpret_cast<const void*>(&dgrad_kernel<KR, true, true>),
-                        reinterpret_cast<const void*>(&dgrad_kernel<KR, true, false>),
-                        reinterpret_cast<const void*>(&dgrad_kernel<KR, false, true>),
-                        reinterpret_cast<const void*>(&dgrad_kernel<KR, false, false>)};
-    int o = 1 << 20;
-    for (const void* f : fs) o = std::min(o, occupancy(f));
-    return o;
-  }();
-  return occ;
-}
-// Row-tile walkers per column group (pw_deep.hip's grid_x): every resident slot once, at most one
-// per tile, a multiple of 8 when that costs no extra tile per walker.
-static int grid_x(int M, int N, int occ) {
-  const int ntiles = (M + TR - 1) / TR;
-  int slots = occ * 256 / (N < NB ? 1 : N / NB);  // (N < NB: the C = 64 fused backward, one column group)
-  if (slots < 1) slots = 1;
-  int gx = std::min(ntiles, slots);
-  const int g8 = gx / 8 * 8;
-  if (g8 >= 8 && (ntiles + g8 - 1) / g8 == (ntiles + gx - 1) / gx) gx = g8;
-  return gx;
+static const PwKernelTable<4, DgradArgs, float*>* bwd_family(int K) {
+  return K == 128 ? &bwd_forms<128>() : K == 256 ? &bwd_forms<256>() : nullptr;
 }
 
 }  // namespace pwd16
 
-// Knob 13 = 0 keeps the tiled engine's bf16 mode for the deep shapes.
+// Knob 13 = 0 keeps the tiled engine's bf16 mode for the deep shapes.  The forward and the dgrad also
+// need the bf16 streaming knob 9 and the streaming knob 3 (their shapes came from the bf16 streaming
+// entries' share); the fused backward needs knob 13 alone.
 static bool pwd16_enabled() { return knob(kKnobPwDeep16) == 1; }
-static bool pwd16_kr(int KR) { return KR == 128 || KR == 256 || KR == 512; }
+static bool pwd16_stream_enabled() { return pwd16_enabled() && knob(kKnobPwsh) == 1 && pw_stream_enabled(); }
 
-// The deep shapes: reduction 128 / 256 / 512, outputs a multiple of 128 columns, 256+ channels on
-// one side when the reduction is 128.
-bool pw_deep16_fwd_ok(int K, int C, int M) {
-  if (!pwd16_enabled() || M <= 0 || !pwd16_kr(C) || K % pwd16::NB || K > 4096 || (C < 256 && K < 256)) return false;
-  return (size_t)M * (K > C ? K : C) * 2 < ((size_t)1 << 31);
+// The deep shapes: reduction 128 / 256 / 512, outputs a multiple of 128 columns (at most 4096), 256+
+// channels on one side.  One partial row per row-tile walker, one channel slice per column group.
+PwPlan pw_deep16_fwd_plan(int M, int K, int C) {
+  if (!pwd16_stream_enabled() || M <= 0 || K % pwd16::NB || K > 4096 || (C < 256 && K < 256)) return {0, 0};
+  if ((size_t)M * (K > C ? K : C) * 2 >= ((size_t)1 << 31)) return {0, 0};
+  const auto* t = pwd16::fwd_family(C);
+  if (!t) return {0, 0};
+  return {pw_deep_grid(M, K, pwd16::NB, pwd16::TR, t->occ), K / pwd16::NB};
 }
-bool pw_deep16_dgrad_ok(int K, int C, int M) {
-  if (!pwd16_enabled() || M <= 0 || !pwd16_kr(K) || C % pwd16::NB || C > 4096 || (K < 256 && C < 256)) return false;
-  return (size_t)M * (K > C ? K : C) * 2 < ((size_t)1 << 31);
+PwPlan pw_deep16_dgrad_plan(int M, int K, int C) {
+  if (!pwd16_stream_enabled() || M <= 0 || C % pwd16::NB || C > 4096 || (K < 256 && C < 256)) return {0, 0};
+  if ((size_t)M * (K > C ? K : C) * 2 >= ((size_t)1 << 31)) return {0, 0};
+  const auto* t = pwd16::dgrad_family(K);
+  if (!t) return {0, 0};
+  return {pw_deep_grid(M, C, pwd16::NB, pwd16::TR, t->occ), C / pwd16::NB};
 }
-int pw_deep16_fwd_rows(int M, int K, int C) {
-#define DK_ROWS(kr) \
-  if (C == kr) return pwd16::grid_x(M, K, pwd16::fwd_occ<kr>());
-  DK_PWD16_KR(DK_ROWS)
-#undef DK_ROWS
-  return 0;
-}
-int pw_deep16_dgrad_rows(int M, int K, int C) {
-#define DK_ROWS(kr) \
-  if (K == kr) return pwd16::grid_x(M, C, pwd16::dgrad_occ<kr>());
-  DK_PWD16_KR(DK_ROWS)
-#undef DK_ROWS
-  return 0;
+// The fused bf16 backward: K in {128, 256}, C a multiple of the block's 128 columns, or K = 128 with
+// C = 64 (one column group, half the block's waves staging only: config 5's 64 -> 128 unit, whose
+// unfused pair stored dy for a side-stream weight GEMM).
+PwPlan pw_deep16_bwd_plan(int M, int K, int C) {
+  if (!pwd16_enabled() || M <= 0 || (C % pwd16::NB && !(K == 128 && C == 64)) || C > 4096) return {0, 0};
+  if ((size_t)M * (K > C ? K : C) * 2 >= ((size_t)1 << 31)) return {0, 0};
+  const auto* t = pwd16::bwd_family(K);
+  if (!t) return {0, 0};
+  return {pw_deep_grid(M, C, pwd16::NB, pwd16::TR, t->occ), C < pwd16::NB ? 1 : C / pwd16::NB};
 }
 
 int pw_deep16_fwd(const bf16_t* x, int M, const float* w, int K, int C, const float* bias, bf16_t* y, const float* im,
-                  const float* iis, const float* ig, const float* ib, int irelu, double* part, hipStream_t st,
-                  const FoldTail* ft) {
+                  const float* iis, const float* ig, const float* ib, int irelu, double* part, PwPlan plan,
+                  hipStream_t st, const FoldTail* ft) {
+  const auto* t = pwd16::fwd_family(C);
+  if (!t || plan.rows == 0) return DK_ERR_ARGS;
   pwd16::FwdArgs a{x, w, bias, y, im, iis, ig, ib, irelu, part, M, K};
   if (ft && part) a.ft = *ft;
   a.nt = nt_stores(kNtPwd16);
-  const dim3 grid(pw_deep16_fwd_rows(M, K, C), K / pwd16::NB);
-  if (grid.x == 0) return DK_ERR_ARGS;
-#define DK_L(kr, B_, S_)                                                                          \
-  do {                                                                                            \
-    if (bias)                                                                                     \
-      hipLaunchKernelGGL((pwd16::fwd_kernel<kr, B_, S_, true>), grid, dim3(pwd16::NT), 0, st, a);  \
-    else                                                                                          \
-      hipLaunchKernelGGL((pwd16::fwd_kernel<kr, B_, S_, false>), grid, dim3(pwd16::NT), 0, st, a); \
-  } while (0)
-#define DK_FWD(kr)               \
-  if (C == kr) {                 \
-    if (im && part)              \
-      DK_L(kr, true, true);      \
-    else if (im)                 \
-      DK_L(kr, true, false);     \
-    else if (part)               \
-      DK_L(kr, false, true);     \
-    else                         \
-      DK_L(kr, false, false);    \
-    return launch_status();      \
-  }
-  DK_PWD16_KR(DK_FWD)
-#undef DK_FWD
-#undef DK_L
-  return DK_ERR_ARGS;
+  t->launch(4 * (im != nullptr) + 2 * (part != nullptr) + (bias != nullptr), dim3(plan.rows, plan.slices), st, a);
+  return launch_status();
 }
 
 int pw_deep16_dgrad_bnbwd(const bf16_t* g, const bf16_t* bn_x, int M, int K, int C, const float* om, const float* ois,
                           const float* og, const float* ob, int orelu, const float* k12, bf16_t* dy_out, const float* w,
                           bf16_t* dx, const bf16_t* res, const bf16_t* x, const float* im, const float* iis,
-                          const float* ig, const float* ib, int irelu, double* part, hipStream_t st,
+                          const float* ig, const float* ib, int irelu, double* part, PwPlan plan, hipStream_t st,
                           const FoldTail* ft) {
+  const auto* t = pwd16::dgrad_family(K);
+  if (!t || plan.rows == 0) return DK_ERR_ARGS;
   pwd16::DgradArgs a{g, bn_x, dy_out, w, dx, res, x, om, ois, og, ob, k12, orelu, im, iis, ig, ib, irelu, part, M, C};
   if (ft && part) a.ft = *ft;
   a.nt = nt_stores(kNtPwd16);
-  const dim3 grid(pw_deep16_dgrad_rows(M, K, C), C / pwd16::NB);
-  if (grid.x == 0) return DK_ERR_ARGS;
-#define DK_L(kr, R_, P_) hipLaunchKernelGGL((pwd16::dgrad_kernel<kr, R_, P_>), grid, dim3(pwd16::NT), 0, st, a)
-#define DK_DG(kr)             \
-  if (K == kr) {              \
-    if (res && x)             \
-      DK_L(kr, true, true);   \
-    else if (res)             \
-      DK_L(kr, true, false);  \
-    else if (x)               \
-      DK_L(kr, false, true);  \
-    else                      \
-      DK_L(kr, false, false); \
-    return launch_status();   \
-  }
-  DK_PWD16_KR(DK_DG)
-#undef DK_DG
-#undef DK_L
-  return DK_ERR_ARGS;
+  t->launch(2 * (res != nullptr) + (x != nullptr), dim3(plan.rows, plan.slices), st, a);
+  return launch_status();
 }
 
-template <int KR>
-static int bwd_occ16() {
-  static const int occ = [] {
-    const void* fs[] = {reinterpret_cast<const void*>(&pwd16::bwd_kernel<KR, true, true>),
-                        reinterpret_cast<const void*>(&pwd16::bwd_kernel<KR, true, false>),
-                        reinterpret_cast<const void*>(&pwd16::bwd_kernel<KR, false, true>),
-                        reinterpret_cast<const void*>(&pwd16::bwd_kernel<KR, false, false>)};
-    int o = 1 << 20;
-    for (const void* f : fs) o = std::min(o, pwd16::occupancy(f));
-    return o;
-  }();
-  return occ;
-}
-// The fused bf16 backward: K in {128, 256}, C a multiple of the block's 128 columns, or K = 128 with
-// C = 64 (one column group, half the block's waves staging only: config 5's 64 -> 128 unit, whose
-// unfused pair stored dy for a side-stream weight GEMM).
-bool pw_deep16_bwd_ok(int K, int C, int M) {
-  if (!pwd16_enabled() || M <= 0 || (K != 128 && K != 256) || (C % pwd16::NB && !(K == 128 && C == 64)) ||
-      C > 4096)
-    return false;
-  return (size_t)M * (K > C ? K : C) * 2 < ((size_t)1 << 31);
-}
-int pw_deep16_bwd_rows(int M, int K, int C) {
-  if (K == 128) return pwd16::grid_x(M, C, bwd_occ16<128>());
-  if (K == 256) return pwd16::grid_x(M, C, bwd_occ16<256>());
-  return 0;
-}
-int pw_deep16_bwd_slices(int M, int K, int C) { return C < pwd16::NB ? 1 : C / pwd16::NB; }
 int pw_deep16_bwd_fused(const bf16_t* g, const bf16_t* bn_x, int M, int K, int C, const float* om, const float* ois,
                         const float* og, const float* ob, int orelu, const float* k12, const float* w, bf16_t* dx,
                         const bf16_t* res, const bf16_t* x, const float* im, const float* iis, const float* ig,
-                        const float* ib, int irelu, double* part, float* wpart, hipStream_t st, const FoldTail* ft) {
+                        const float* ib, int irelu, double* part, float* wpart, PwPlan plan, hipStream_t st,
+                        const FoldTail* ft) {
   if (!x || (im != nullptr) != (part != nullptr)) return DK_ERR_ARGS;
+  const auto* t = pwd16::bwd_family(K);
+  if (!t || plan.rows == 0) return DK_ERR_ARGS;
   pwd16::DgradArgs a{g, bn_x, nullptr, w, dx, res, x, om, ois, og, ob, k12, orelu, im, iis, ig, ib, irelu, part, M, C};
   if (ft && part) a.ft = *ft;
   a.nt = nt_stores(kNtPwd16);
-  const dim3 grid(pw_deep16_bwd_rows(M, K, C), pw_deep16_bwd_slices(M, K, C));
-  if (grid.x == 0) return DK_ERR_ARGS;
-#define DK_L(kr, R_, B_) hipLaunchKernelGGL((pwd16::bwd_kernel<kr, R_, B_>), grid, dim3(pwd16::NT), 0, st, a, wpart)
-#define DK_BW(kr)             \
-  if (K == kr) {              \
-    if (res && im)            \
-      DK_L(kr, true, true);   \
-    else if (res)             \
-      DK_L(kr, true, false);  \
-    else if (im)              \
-      DK_L(kr, false, true);  \
-    else                      \
-      DK_L(kr, false, false); \
-    return launch_status();   \
-  }
-  DK_BW(128)
-  DK_BW(256)
-#undef DK_BW
-#undef DK_L
-  return DK_ERR_ARGS;
+  t->launch(2 * (res != nullptr) + (im != nullptr), dim3(plan.rows, plan.slices), st, a, wpart);
+  return launch_status();
 }
 
 }  // namespace dk

@@ -28,8 +28,8 @@
 
 #include <type_traits>
 
-#include "dk_common.h"
 #include "fold_tail.h"
+#include "pw_launch.h"
 
 namespace dk {
 namespace pws {
@@ -526,57 +526,21 @@ __global__ __launch_bounds__(256, KR_ == 64 ? 3 : 2) void fwd_kernel(FwdArgs a) 
   }
 }
 
-// Resident blocks per CU of a family of instantiations (the smallest; queried once per family).
-static int min_occupancy(const void* const* fs, int n) {
-  int o = 1 << 20;
-  for (int i = 0; i < n; ++i) {
-    int v = 0;
-    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&v, fs[i], 256, 0) != hipSuccess || v < 1) v = 1;
-    o = v < o ? v : o;
-  }
-  return o;
+// dgrad_bnbwd_kernel's forms: index 2 RES + PART.
+static const PwKernelTable<4, DgradArgs>& dgrad_forms() {
+  static const auto t = pw_table(PwKernelTable<4, DgradArgs>{
+      {&dgrad_bnbwd_kernel<false, false>, &dgrad_bnbwd_kernel<false, true>, &dgrad_bnbwd_kernel<true, false>,
+       &dgrad_bnbwd_kernel<true, true>},
+      256, 0xFu});
+  return t;
 }
 
-// Blocks of a persistent grid: every resident slot once, at most one block per 4 tiles.  The
-// count depends only on M and the (fixed) occupancy, so the partial-row count a caller
-// allocates for is the count the launch uses, and the summation order is reproducible.
-static int grid_blocks(int M, int occ) {
-  const int ntiles = (M + TR - 1) / TR;
-  const int want = (ntiles + WAVES - 1) / WAVES;
-  const int slots = occ * 256;
-  return want < slots ? (want > 0 ? want : 1) : slots;
-}
-
-int dgrad_blocks(int M) {
-  // thread-safe one-time query (a function-local static initialised once)
-  static const int occ = [] {
-    const void* fs[] = {reinterpret_cast<const void*>(&dgrad_bnbwd_kernel<false, false>),
-                        reinterpret_cast<const void*>(&dgrad_bnbwd_kernel<false, true>),
-                        reinterpret_cast<const void*>(&dgrad_bnbwd_kernel<true, false>),
-                        reinterpret_cast<const void*>(&dgrad_bnbwd_kernel<true, true>)};
-    return min_occupancy(fs, 4);
-  }();
-  return grid_blocks(M, occ);
-}
-
+// fwd_kernel's forms at K = C = KR_: index 4 BN + 2 STATS + STRIDED.
 template <int KR_>
-static int fwd_occ() {
-  // thread-safe one-time query (a function-local static initialised once)
-  static const int occ = [] {
-    const void* fs[] = {reinterpret_cast<const void*>(&fwd_kernel<KR_, KR_, true, true, true>),
-                        reinterpret_cast<const void*>(&fwd_kernel<KR_, KR_, true, true, false>),
-                        reinterpret_cast<const void*>(&fwd_kernel<KR_, KR_, true, false, true>),
-                        reinterpret_cast<const void*>(&fwd_kernel<KR_, KR_, true, false, false>),
-                        reinterpret_cast<const void*>(&fwd_kernel<KR_, KR_, false, true, true>),
-                        reinterpret_cast<const void*>(&fwd_kernel<KR_, KR_, false, true, false>),
-                        reinterpret_cast<const void*>(&fwd_kernel<KR_, KR_, false, false, true>),
-                        reinterpret_cast<const void*>(&fwd_kernel<KR_, KR_, false, false, false>)};
-    return min_occupancy(fs, 8);
-  }();
-  return occ;
+static const PwKernelTable<8, FwdArgs>& fwd_forms() {
+  static const auto t = pw_table(PwKernelTable<8, FwdArgs>{{DK_PW_F3(fwd_kernel, KR_, KR_)}, 256, 0xFFu});
+  return t;
 }
-
-int fwd_blocks(int M, int KC) { return grid_blocks(M, KC == 128 ? fwd_occ<128>() : fwd_occ<64>()); }
 
 // ---------------------------------------------------------------------------------------
 // dk_pwconv_bwd_bnbwd_f32 at K = C = 64: the whole backward of a stride-1 pointwise layer whose
@@ -914,50 +878,53 @@ __global__ __launch_bounds__(256, PF ? 1 : 2) void bwd_fused_kernel(BwdArgs ba) 
   }
 }
 
-// The backward's A-operand prefetch: off (2 waves per SIMD; whole step 9.12 -> 9.02 ms,
-// scripts/ab_step.py, r03) except in the residual and lattice variants, which spill without it.
-static int bwd_fused_occ() {
-  // thread-safe one-time query (a function-local static initialised once)
-  static const int occ = [] {
-    const void* fs[] = {reinterpret_cast<const void*>(&bwd_fused_kernel<false, true, true, false>),
-                        reinterpret_cast<const void*>(&bwd_fused_kernel<false, false, true, false>),
-                        reinterpret_cast<const void*>(&bwd_fused_kernel<false, false, false, false>)};
-    return min_occupancy(fs, 3);
-  }();
-  return occ;
+// bwd_fused_kernel's forms: index 3 RES + (PART ? 2 : BNIN) (PART needs BNIN), then the two lattice
+// forms (6 + PART).  The A-operand prefetch is off (2 waves per SIMD; whole step 9.12 -> 9.02 ms,
+// scripts/ab_step.py, r03) except in the residual and lattice forms, which spill without it.
+static const PwKernelTable<8, BwdArgs>& bwd_fused_forms() {
+  static const auto t = pw_table(PwKernelTable<8, BwdArgs>{
+      {&bwd_fused_kernel<false, false, false, false>, &bwd_fused_kernel<false, false, true, false>,
+       &bwd_fused_kernel<false, true, true, false>,
+       // not counted: the residual forms prefetch (one wave per SIMD, a lower occupancy); on the grid of
+       // the others a block count above their occupancy only adds a second round of blocks, it never
+       // changes the order of the results
+       &bwd_fused_kernel<true, false, false, true>, &bwd_fused_kernel<true, false, true, true>,
+       &bwd_fused_kernel<true, true, true, true>,
+       // not counted: the lattice forms prefetch too and share the rows of dk_pwconv_bwd_fused_rows
+       &bwd_fused_kernel<false, false, true, true, true>, &bwd_fused_kernel<false, true, true, true, true>},
+      256, 0x07u});
+  return t;
 }
-
-int bwd_fused_blocks(int M) { return grid_blocks(M, bwd_fused_occ()); }
-// (the grid of a residual variant, which always prefetches, follows the same count: a block count
-// above its occupancy only adds a second partial round of blocks, never changes the results' order)
 }  // namespace pws
 
 // knob kKnobPwStream (default on; kind 3)
 bool pw_stream_enabled() { return knob(kKnobPwStream) == 1; }
 
-// Shapes the streaming dgrad takes (the rest go to the tiled engine).
-bool pw_stream_dgrad_ok(int K, int C, int M) {
-  if (!pw_stream_enabled()) return false;
-  return K == pws::KR && C == pws::NO && M > 0 && (size_t)M * 64 * 4 < ((size_t)1 << 31);
+// The shapes the streaming kernels take (the rest go to the tiled engine): K = C = 64, the forward
+// also K = C = 128.  One block writes one partial row; one channel slice.
+static bool pws_dgrad_shape(int M, int K, int C) {
+  return pw_stream_enabled() && K == pws::KR && C == pws::NO && M > 0 && (size_t)M * 64 * 4 < ((size_t)1 << 31);
 }
-
-int pw_stream_dgrad_rows(int M) { return pws::dgrad_blocks(M); }
-
-bool pw_stream_fwd_ok(int K, int C, int M, size_t xbytes) {
-  if (!pw_stream_enabled()) return false;
+PwPlan pw_stream_dgrad_plan(int M, int K, int C) {
+  if (!pws_dgrad_shape(M, K, C)) return {0, 0};
+  return {pw_stream_grid(M, pws::TR, pws::WAVES, pws::dgrad_forms().occ), 1};
+}
+PwPlan pw_stream_bwd_plan(int M, int K, int C) {
+  if (!pws_dgrad_shape(M, K, C)) return {0, 0};
+  return {pw_stream_grid(M, pws::TR, pws::WAVES, pws::bwd_fused_forms().occ), 1};
+}
+PwPlan pw_stream_fwd_plan(int M, int K, int C, size_t xbytes) {
   const bool shape = (K == 64 && C == 64) || (K == 128 && C == 128);
-  return shape && M > 0 && xbytes < ((size_t)1 << 31) && (size_t)M * K * 4 < ((size_t)1 << 31);
+  if (!pw_stream_enabled() || !shape || M <= 0 || xbytes >= ((size_t)1 << 31) || (size_t)M * K * 4 >= ((size_t)1 << 31))
+    return {0, 0};
+  return {pw_stream_grid(M, pws::TR, pws::WAVES, (K == 128 ? pws::fwd_forms<128>() : pws::fwd_forms<64>()).occ), 1};
 }
-int pw_stream_fwd_rows(int M, int K) { return pws::fwd_blocks(M, K); }
-
-bool pw_stream_bwd_ok(int K, int C, int M) { return pw_stream_dgrad_ok(K, C, M); }
-int pw_stream_bwd_rows(int M) { return pws::bwd_fused_blocks(M); }
 
 int pw_stream_bwd_fused(const float* g, const float* bn_x, int M, const float* om, const float* ois,
                         const float* og, const float* ob, int orelu, const float* k12, const float* w, float* dx,
                         const float* res, const float* x, const float* im, const float* iis, const float* ig,
                         const float* ib, int irelu, double* part, const float* bm, const float* bis,
-                        const float* bgm, const float* bbt, int brelu, float* wpart, hipStream_t st,
+                        const float* bgm, const float* bbt, int brelu, float* wpart, PwPlan plan, hipStream_t st,
                         const FoldTail* ft, const int* lattice) {
   pws::BwdArgs a{{g, bn_x, nullptr, w, dx, res, x, om, ois, og, ob, k12, orelu, im, iis, ig, ib, irelu, part, M},
                  bm, bis, bgm, bbt, brelu, wpart, 0, 0, 0, 0, 0};
@@ -971,74 +938,25 @@ int pw_stream_bwd_fused(const float* g, const float* bn_x, int M, const float* o
   }
   if (ft && part) a.d.ft = *ft;
   a.d.nt = nt_stores(kNtPwsBwd);
-  const dim3 grid(pws::bwd_fused_blocks(M));
   const bool r = res != nullptr, pt = part != nullptr, bn = bm != nullptr;
   if (pt && !bn) return DK_ERR_ARGS;
   // the partials' BatchNorm is the weight-gradient operand's (the kernel computes its terms once)
   if (pt && (im != bm || iis != bis || ig != bgm || ib != bbt || (irelu != 0) != (brelu != 0))) return DK_ERR_ARGS;
-  if (lattice) {  // (the lattice form keeps the prefetch: without it it spills at 2 waves per SIMD)
-    if (pt)
-      hipLaunchKernelGGL((pws::bwd_fused_kernel<false, true, true, true, true>), grid, dim3(256), 0, st, a);
-    else
-      hipLaunchKernelGGL((pws::bwd_fused_kernel<false, false, true, true, true>), grid, dim3(256), 0, st, a);
-    return launch_status();
-  }
-  // (the residual variants keep the prefetch: without it they spill at 2 waves per SIMD)
-#define DK_BWD(R_, P_, B_) hipLaunchKernelGGL((pws::bwd_fused_kernel<R_, P_, B_, R_>), grid, dim3(256), 0, st, a)
-  if (pt) {
-    if (r) {
-      DK_BWD(true, true, true);
-    } else {
-      DK_BWD(false, true, true);
-    }
-  } else if (bn) {
-    if (r) {
-      DK_BWD(true, false, true);
-    } else {
-      DK_BWD(false, false, true);
-    }
-  } else {
-    if (r) {
-      DK_BWD(true, false, false);
-    } else {
-      DK_BWD(false, false, false);
-    }
-  }
-#undef DK_BWD
+  pws::bwd_fused_forms().launch(lattice ? 6 + pt : 3 * r + (pt ? 2 : bn), dim3(plan.rows), st, a);
   return launch_status();
 }
 
 int pw_stream_fwd(const float* x, int N, int H, int W, int stride, int OH, int OW, const float* w, int KC,
                   const float* bias, float* y, const float* im, const float* iis, const float* ig,
-                  const float* ib, int irelu, double* part, hipStream_t st, const FoldTail* ft) {
-  if (KC != 64 && KC != 128) return DK_ERR_ARGS;
+                  const float* ib, int irelu, double* part, PwPlan plan, hipStream_t st, const FoldTail* ft) {
+  if (plan.rows == 0) return DK_ERR_ARGS;
   const int M = N * OH * OW;
   pws::FwdArgs a{x, w, bias, y, im, iis, ig, ib, irelu, part, M, H, W, OH, OW, stride,
                  (uint32_t)((size_t)N * H * W * KC * 4)};
   if (ft && part) a.ft = *ft;
   a.nt = nt_stores(kNtPwsFwd);
-  const dim3 grid(pws::fwd_blocks(M, KC));
-  const bool strided = stride != 1;
-#define DK_FWD(BN_, ST_)                                                                                \
-  if (KC == 128) {                                                                                      \
-    if (strided)                                                                                        \
-      hipLaunchKernelGGL((pws::fwd_kernel<128, 128, BN_, ST_, true>), grid, dim3(256), 0, st, a);       \
-    else                                                                                                \
-      hipLaunchKernelGGL((pws::fwd_kernel<128, 128, BN_, ST_, false>), grid, dim3(256), 0, st, a);      \
-  } else if (strided)                                                                                   \
-    hipLaunchKernelGGL((pws::fwd_kernel<64, 64, BN_, ST_, true>), grid, dim3(256), 0, st, a);           \
-  else                                                                                                  \
-    hipLaunchKernelGGL((pws::fwd_kernel<64, 64, BN_, ST_, false>), grid, dim3(256), 0, st, a);
-  if (im && part) {
-    DK_FWD(true, true)
-  } else if (im) {
-    DK_FWD(true, false)
-  } else if (part) {
-    DK_FWD(false, true)
-  } else {
-    DK_FWD(false, false)
-  }
-#undef DK_FWD
+  const int form = 4 * (im != nullptr) + 2 * (part != nullptr) + (stride != 1);
+  (KC == 128 ? pws::fwd_forms<128>() : pws::fwd_forms<64>()).launch(form, dim3(plan.rows), st, a);
   return launch_status();
 }
 
@@ -1046,19 +964,11 @@ int pw_stream_dgrad_bnbwd(const float* g, const float* bn_x, int M, const float*
                           const float* og, const float* ob, int orelu, const float* k12, float* dy_out,
                           const float* w, float* dx, const float* res, const float* x, const float* im,
                           const float* iis, const float* ig, const float* ib, int irelu, double* part,
-                          hipStream_t st, const FoldTail* ft) {
+                          PwPlan plan, hipStream_t st, const FoldTail* ft) {
   pws::DgradArgs a{g, bn_x, dy_out, w, dx, res, x, om, ois, og, ob, k12, orelu, im, iis, ig, ib, irelu, part, M};
   if (ft && part) a.ft = *ft;
   a.nt = nt_stores(kNtPwsDgrad);
-  const dim3 grid(pws::dgrad_blocks(M));
-  if (res && x)
-    hipLaunchKernelGGL((pws::dgrad_bnbwd_kernel<true, true>), grid, dim3(256), 0, st, a);
-  else if (res)
-    hipLaunchKernelGGL((pws::dgrad_bnbwd_kernel<true, false>), grid, dim3(256), 0, st, a);
-  else if (x)
-    hipLaunchKernelGGL((pws::dgrad_bnbwd_kernel<false, true>), grid, dim3(256), 0, st, a);
-  else
-    hipLaunchKernelGGL((pws::dgrad_bnbwd_kernel<false, false>), grid, dim3(256), 0, st, a);
+  pws::dgrad_forms().launch(2 * (res != nullptr) + (x != nullptr), dim3(plan.rows), st, a);
   return launch_status();
 }
 

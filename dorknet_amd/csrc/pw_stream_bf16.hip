@@ -17,8 +17,8 @@
 // in ascending order, k = 16s + 8h + j on both operands), the same fp32 epilogue, RNE stores, and
 // statistics over the stored (rounded) values.  Only the grouping of the fp64 partial sums
 // differs (one row per block instead of one per 64-pixel tile).
-#include "dk_common.h"
 #include "fold_tail.h"
+#include "pw_launch.h"
 
 namespace dk {
 namespace pwsh {
@@ -40,25 +40,6 @@ __device__ __forceinline__ u32x4 pack8(f32x4 lo, f32x4 hi) {
 }
 __device__ __forceinline__ bf16x8 frag(u32x4 u) { return __builtin_bit_cast(bf16x8, u); }
 __device__ __forceinline__ uint16_t bf16_bits(float v) { return __builtin_bit_cast(uint16_t, (__bf16)v); }
-
-// Resident blocks per CU of a family of instantiations (the smallest).
-static int min_occupancy(const void* const* fs, int n, int threads = 256) {
-  int o = 1 << 20;
-  for (int i = 0; i < n; ++i) {
-    int v = 0;
-    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&v, fs[i], threads, 0) != hipSuccess || v < 1) v = 1;
-    o = v < o ? v : o;
-  }
-  return o;
-}
-// A persistent grid: every resident slot once, at most one block per 4 tiles; a function of M and
-// the (fixed) occupancy only, so callers allocate exactly the partial rows the launch writes.
-static int grid_blocks(int M, int occ) {
-  const int ntiles = (M + TR - 1) / TR;
-  const int want = (ntiles + WAVES - 1) / WAVES;
-  const int slots = occ * 256;
-  return want < slots ? (want > 0 ? want : 1) : slots;
-}
 
 // ---------------------------------------------------------------------------------------
 // Forward (layers/pointwise_convolution.py:46-55): y = bn(x) . W^T with the preceding BatchNorm
@@ -702,165 +683,101 @@ __global__ __launch_bounds__(256, 2) void bwd_fused_kernel(BwdArgs ba) {
   if (a.ft.part) fold_tail<256>(a.ft, blockIdx.x, 0, NO, 0);
 }
 
+// fwd_kernel's forms at reduction KR, NO outputs: index 2 BN + STATS.
 template <int KR, int NO>
-static int fwd_occ() {
-  // thread-safe one-time query (a function-local static initialised once)
-  static const int occ = [] {
-    const void* fs[] = {reinterpret_cast<const void*>(&fwd_kernel<KR, NO, true, true>),
-                        reinterpret_cast<const void*>(&fwd_kernel<KR, NO, true, false>),
-                        reinterpret_cast<const void*>(&fwd_kernel<KR, NO, false, true>),
-                        reinterpret_cast<const void*>(&fwd_kernel<KR, NO, false, false>)};
-    return min_occupancy(fs, 4);
-  }();
-  return occ;
+static const PwKernelTable<4, FwdArgs>& fwd_forms() {
+  static const auto t = pw_table(PwKernelTable<4, FwdArgs>{{DK_PW_F2(fwd_kernel, KR, NO)}, 256, 0xFu});
+  return t;
 }
+// dgrad_bnbwd_kernel's forms: index 2 RES + PART.
 template <int KR, int NO>
-static int dgrad_occ() {
-  // thread-safe one-time query (a function-local static initialised once)
-  static const int occ = [] {
-    const void* fs[] = {reinterpret_cast<const void*>(&dgrad_bnbwd_kernel<KR, NO, true, true>),
-                        reinterpret_cast<const void*>(&dgrad_bnbwd_kernel<KR, NO, true, false>),
-                        reinterpret_cast<const void*>(&dgrad_bnbwd_kernel<KR, NO, false, true>),
-                        reinterpret_cast<const void*>(&dgrad_bnbwd_kernel<KR, NO, false, false>)};
-    return min_occupancy(fs, 4);
-  }();
-  return occ;
+static const PwKernelTable<4, DgradArgs>& dgrad_forms() {
+  static const auto t = pw_table(PwKernelTable<4, DgradArgs>{{DK_PW_F2(dgrad_bnbwd_kernel, KR, NO)}, 256, 0xFu});
+  return t;
+}
+// bwd_fused_kernel's forms (K = C = 64): index 2 RES + PART.
+static const PwKernelTable<4, BwdArgs>& bwd_fused_forms() {
+  static const auto t = pw_table(PwKernelTable<4, BwdArgs>{
+      {&bwd_fused_kernel<false, false>, &bwd_fused_kernel<false, true>, &bwd_fused_kernel<true, false>,
+       &bwd_fused_kernel<true, true>},
+      256, 0xFu});
+  return t;
 }
 
-
-// The (reduction, output) channel pairs instantiated.
-#define DK_PWSH_SHAPES(X) X(64, 64) X(64, 128) X(128, 64) X(128, 128)
+// The family of a (reduction, output) channel pair: both in {64, 128} (nullptr: not instantiated).
+static const PwKernelTable<4, FwdArgs>* fwd_family(int KR, int NO) {
+  if (KR == 64) return NO == 64 ? &fwd_forms<64, 64>() : NO == 128 ? &fwd_forms<64, 128>() : nullptr;
+  if (KR == 128) return NO == 64 ? &fwd_forms<128, 64>() : NO == 128 ? &fwd_forms<128, 128>() : nullptr;
+  return nullptr;
+}
+static const PwKernelTable<4, DgradArgs>* dgrad_family(int KR, int NO) {
+  if (KR == 64) return NO == 64 ? &dgrad_forms<64, 64>() : NO == 128 ? &dgrad_forms<64, 128>() : nullptr;
+  if (KR == 128) return NO == 64 ? &dgrad_forms<128, 64>() : NO == 128 ? &dgrad_forms<128, 128>() : nullptr;
+  return nullptr;
+}
 
 }  // namespace pwsh
 
 // Knob 9 = 0 (or the fp32 streaming knob 3 = 0) keeps the tiled engine.
 // (knob kKnobPwsh, kind 9)
 static bool pwsh_enabled() { return knob(kKnobPwsh) == 1 && pw_stream_enabled(); }
+static bool pwsh_size_ok(int M, int K, int C) { return M > 0 && (size_t)M * (K > C ? K : C) * 2 < ((size_t)1 << 31); }
 
-static bool pwsh_shape(int KR, int NO) { return (KR == 64 || KR == 128) && (NO == 64 || NO == 128); }
-constexpr int kDeepCols = 128;  // output columns per block of the deep kernels (pw_deep_bf16.hip)
-// The deep shapes (reduction or outputs of 256+) go to the weight-stationary kernels of
-// pw_deep_bf16.hip (knob 13); with those off they stay on the tiled engine.
-bool pw_stream_bf16_fwd_ok(int K, int C, int M) {
-  return pwsh_enabled() && (pwsh_shape(C, K) || pw_deep16_fwd_ok(K, C, M)) && M > 0 &&
-         (size_t)M * (K > C ? K : C) * 2 < ((size_t)1 << 31);
+// K, C in {64, 128} (the deep shapes, a side of 256+, are pw_deep_bf16.hip's): one block writes one
+// partial row; one channel slice.
+PwPlan pw_stream_bf16_fwd_plan(int M, int K, int C) {
+  if (!pwsh_enabled() || !pwsh_size_ok(M, K, C)) return {0, 0};
+  const auto* t = pwsh::fwd_family(C, K);
+  if (!t) return {0, 0};
+  return {pw_stream_grid(M, pwsh::TR, pwsh::WAVES, t->occ), 1};
 }
-int pw_stream_bf16_fwd_rows(int M, int K, int C) {
-  if (!pwsh_shape(C, K) && pw_deep16_fwd_ok(K, C, M)) return pw_deep16_fwd_rows(M, K, C);
-#define DK_ROWS(kr, no) \
-  if (C == kr && K == no) return pwsh::grid_blocks(M, pwsh::fwd_occ<kr, no>());
-  DK_PWSH_SHAPES(DK_ROWS)
-#undef DK_ROWS
-  return 0;
+PwPlan pw_stream_bf16_dgrad_plan(int M, int K, int C) {
+  if (!pwsh_enabled() || !pwsh_size_ok(M, K, C)) return {0, 0};
+  const auto* t = pwsh::dgrad_family(K, C);
+  if (!t) return {0, 0};
+  return {pw_stream_grid(M, pwsh::TR, pwsh::WAVES, t->occ), 1};
 }
-int pw_stream_bf16_fwd_slices(int K, int C) { return pwsh_shape(C, K) ? 1 : K / kDeepCols; }
-bool pw_stream_bf16_dgrad_ok(int K, int C, int M) {
-  return pwsh_enabled() && (pwsh_shape(K, C) || pw_deep16_dgrad_ok(K, C, M)) && M > 0 &&
-         (size_t)M * (K > C ? K : C) * 2 < ((size_t)1 << 31);
+// the fused K = C = 64 backward (bwd_fused_kernel)
+PwPlan pw_stream_bf16_bwd_plan(int M, int K, int C) {
+  if (!pwsh_enabled() || K != 64 || C != 64 || M <= 0 || (size_t)M * 64 * 2 >= ((size_t)1 << 31)) return {0, 0};
+  return {pw_stream_grid(M, pwsh::TR, pwsh::WAVES, pwsh::bwd_fused_forms().occ), 1};
 }
-int pw_stream_bf16_dgrad_rows(int M, int K, int C) {
-  if (!pwsh_shape(K, C) && pw_deep16_dgrad_ok(K, C, M)) return pw_deep16_dgrad_rows(M, K, C);
-#define DK_ROWS(kr, no) \
-  if (K == kr && C == no) return pwsh::grid_blocks(M, pwsh::dgrad_occ<kr, no>());
-  DK_PWSH_SHAPES(DK_ROWS)
-#undef DK_ROWS
-  return 0;
-}
-int pw_stream_bf16_dgrad_slices(int K, int C) { return pwsh_shape(K, C) ? 1 : C / kDeepCols; }
 
 int pw_stream_bf16_fwd(const bf16_t* x, int M, const float* w, int K, int C, const float* bias, bf16_t* y,
                        const float* im, const float* iis, const float* ig, const float* ib, int irelu, double* part,
-                       hipStream_t st, const FoldTail* ft) {
-  if (!pwsh_shape(C, K) && pw_deep16_fwd_ok(K, C, M))  // the weight-stationary kernels (pw_deep_bf16.hip)
-    return pw_deep16_fwd(x, M, w, K, C, bias, y, im, iis, ig, ib, irelu, part, st, ft);
-  if (!pwsh_shape(C, K)) return DK_ERR_ARGS;
+                       PwPlan plan, hipStream_t st, const FoldTail* ft) {
+  const auto* t = pwsh::fwd_family(C, K);
+  if (!t || plan.rows == 0) return DK_ERR_ARGS;
   pwsh::FwdArgs a{x, w, bias, y, im, iis, ig, ib, irelu, part, M};
   if (ft && part) a.ft = *ft;
-  const dim3 grid(pw_stream_bf16_fwd_rows(M, K, C));
-  if (grid.x == 0) return DK_ERR_ARGS;
-#define DK_FWD(kr, no)                                                                                   \
-  if (C == kr && K == no) {                                                                              \
-    if (im && part)                                                                                      \
-      hipLaunchKernelGGL((pwsh::fwd_kernel<kr, no, true, true>), grid, dim3(256), 0, st, a);             \
-    else if (im)                                                                                         \
-      hipLaunchKernelGGL((pwsh::fwd_kernel<kr, no, true, false>), grid, dim3(256), 0, st, a);            \
-    else if (part)                                                                                       \
-      hipLaunchKernelGGL((pwsh::fwd_kernel<kr, no, false, true>), grid, dim3(256), 0, st, a);            \
-    else                                                                                                 \
-      hipLaunchKernelGGL((pwsh::fwd_kernel<kr, no, false, false>), grid, dim3(256), 0, st, a);           \
-    return launch_status();                                                                              \
-  }
-  DK_PWSH_SHAPES(DK_FWD)
-#undef DK_FWD
-  return DK_ERR_ARGS;
+  t->launch(2 * (im != nullptr) + (part != nullptr), dim3(plan.rows), st, a);
+  return launch_status();
 }
 
 int pw_stream_bf16_dgrad_bnbwd(const bf16_t* g, const bf16_t* bn_x, int M, int K, int C, const float* om,
                                const float* ois, const float* og, const float* ob, int orelu, const float* k12,
                                bf16_t* dy_out, const float* w, bf16_t* dx, const bf16_t* res, const bf16_t* x,
                                const float* im, const float* iis, const float* ig, const float* ib, int irelu,
-                               double* part, hipStream_t st, const FoldTail* ft) {
-  if (!pwsh_shape(K, C) && pw_deep16_dgrad_ok(K, C, M))
-    return pw_deep16_dgrad_bnbwd(g, bn_x, M, K, C, om, ois, og, ob, orelu, k12, dy_out, w, dx, res, x, im, iis, ig, ib,
-                                 irelu, part, st, ft);
-  if (!pwsh_shape(K, C)) return DK_ERR_ARGS;
+                               double* part, PwPlan plan, hipStream_t st, const FoldTail* ft) {
+  const auto* t = pwsh::dgrad_family(K, C);
+  if (!t || plan.rows == 0) return DK_ERR_ARGS;
   pwsh::DgradArgs a{g, bn_x, dy_out, w, dx, res, x, om, ois, og, ob, k12, orelu, im, iis, ig, ib, irelu, part, M};
   if (ft && part) a.ft = *ft;
-  const dim3 grid(pw_stream_bf16_dgrad_rows(M, K, C));
-  if (grid.x == 0) return DK_ERR_ARGS;
-#define DK_DG(kr, no)                                                                                    \
-  if (K == kr && C == no) {                                                                              \
-    if (res && x)                                                                                        \
-      hipLaunchKernelGGL((pwsh::dgrad_bnbwd_kernel<kr, no, true, true>), grid, dim3(256), 0, st, a);     \
-    else if (res)                                                                                        \
-      hipLaunchKernelGGL((pwsh::dgrad_bnbwd_kernel<kr, no, true, false>), grid, dim3(256), 0, st, a);    \
-    else if (x)                                                                                          \
-      hipLaunchKernelGGL((pwsh::dgrad_bnbwd_kernel<kr, no, false, true>), grid, dim3(256), 0, st, a);    \
-    else                                                                                                 \
-      hipLaunchKernelGGL((pwsh::dgrad_bnbwd_kernel<kr, no, false, false>), grid, dim3(256), 0, st, a);   \
-    return launch_status();                                                                              \
-  }
-  DK_PWSH_SHAPES(DK_DG)
-#undef DK_DG
-  return DK_ERR_ARGS;
+  t->launch(2 * (res != nullptr) + (x != nullptr), dim3(plan.rows), st, a);
+  return launch_status();
 }
-
-// ---- the fused K = C = 64 backward (bwd_fused_kernel) ----
-static int pwsh_bwd_occ() {
-  static const int occ = [] {
-    const void* fs[] = {reinterpret_cast<const void*>(&pwsh::bwd_fused_kernel<true, true>),
-                        reinterpret_cast<const void*>(&pwsh::bwd_fused_kernel<true, false>),
-                        reinterpret_cast<const void*>(&pwsh::bwd_fused_kernel<false, true>),
-                        reinterpret_cast<const void*>(&pwsh::bwd_fused_kernel<false, false>)};
-    return pwsh::min_occupancy(fs, 4);
-  }();
-  return occ;
-}
-bool pw_stream_bf16_bwd_ok(int K, int C, int M) {
-  return pwsh_enabled() && K == 64 && C == 64 && M > 0 &&
-         (size_t)M * 64 * 2 < ((size_t)1 << 31);
-}
-int pw_stream_bf16_bwd_rows(int M) { return pwsh::grid_blocks(M, pwsh_bwd_occ()); }
 
 int pw_stream_bf16_bwd_fused(const bf16_t* g, const bf16_t* bn_x, int M, const float* om, const float* ois,
                              const float* og, const float* ob, int orelu, const float* k12, const float* w, bf16_t* dx,
                              const bf16_t* res, const bf16_t* x, const float* im, const float* iis, const float* ig,
-                             const float* ib, int irelu, double* part, float* wpart, hipStream_t st,
+                             const float* ib, int irelu, double* part, float* wpart, PwPlan plan, hipStream_t st,
                              const FoldTail* ft) {
   if (!x || (part && !im)) return DK_ERR_ARGS;
   pwsh::BwdArgs a{pwsh::DgradArgs{g, bn_x, nullptr, w, dx, res, x, om, ois, og, ob, k12, orelu, im, iis, ig, ib, irelu,
                                   part, M},
                   wpart};
   if (ft && part) a.d.ft = *ft;
-  const dim3 grid(pw_stream_bf16_bwd_rows(M));
-  if (res && part)
-    hipLaunchKernelGGL((pwsh::bwd_fused_kernel<true, true>), grid, dim3(256), 0, st, a);
-  else if (res)
-    hipLaunchKernelGGL((pwsh::bwd_fused_kernel<true, false>), grid, dim3(256), 0, st, a);
-  else if (part)
-    hipLaunchKernelGGL((pwsh::bwd_fused_kernel<false, true>), grid, dim3(256), 0, st, a);
-  else
-    hipLaunchKernelGGL((pwsh::bwd_fused_kernel<false, false>), grid, dim3(256), 0, st, a);
+  pwsh::bwd_fused_forms().launch(2 * (res != nullptr) + (part != nullptr), dim3(plan.rows), st, a);
   return launch_status();
 }
 

@@ -1,8 +1,9 @@
 #!/bin/bash
 # A/B of two builds of the library on one box: dorknet_amd/lib/libdorknet_hip_base.so (the baseline)
 # against dorknet_amd/lib/libdorknet_hip.so, alternating, for a config.  Usage: bash scripts/ab_builds.sh CONFIG ROUNDS
-# BASE_ENV (optional, e.g. "DORKNET_DW_STRIDED_BN=0"): environment for the baseline runs, for Python paths the
-# baseline build lacks.
+# BASE_ENV (optional, one VAR=VALUE): environment for the baseline runs, for Python paths the baseline build
+# lacks.  (The C library reads no environment variable: its paths are chosen by dk_debug_set_gemm_config, here
+# through ab_step.py --knob.)
 set -u
 CFG=${1:-3}; ROUNDS=${2:-3}
 ROOT=$(pwd); BASE=$ROOT/dorknet_amd/lib/libdorknet_hip_base.so; NEW=$ROOT/dorknet_amd/lib/libdorknet_hip.so

@@ -1,7 +1,10 @@
 """Per-shape timing of the fused pointwise backward (dk_pwconv_bwd_bnbwd_f32) against the
 unfused pair it replaces (dk_pwconv_dgrad_bnbwd_f32 + dk_pwconv_wgrad_bnx_f32), bs=256.
 
-    DORKNET_PWF_PREFETCH=0|1 python scripts/pwf_bench.py
+    python scripts/pwf_bench.py
+
+The path a shape takes is chosen by the tuning knobs (dk_debug_set_gemm_config, include/dorknet_hip.h;
+`bench.py --knob KIND=V` for a whole step); no environment variable reaches them.
 """
 import os
 import sys

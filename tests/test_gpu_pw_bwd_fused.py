@@ -79,6 +79,41 @@ def test_pointwise_bwd_fused(K, C, relu, bn_in, resid, shape):
         assert float((s1 - s0).norm() / s0.norm()) < 1e-12
 
 
+@pytest.mark.parametrize("bn,resid", [(False, False), (True, False), (False, True), (True, True)])
+def test_every_launch_form_at_small_shapes(bn, resid):
+    """The streaming bwd_fused_kernel forms (pw_stream.hip, K = C = 64) that no case above reaches: no
+    input BatchNorm, or an input BatchNorm without its partials, each with and without a residual
+    (the cases above always ask for the partials with the BatchNorm), at 2 x 5 x 7 = 70 pixels (a
+    ragged last 32-pixel tile, three tiles).  Against the unfused pair, as above."""
+    K = C = 64
+    N, H, W = 2, 5, 7
+    rng = np.random.RandomState(7 + bn + 2 * resid)
+    xo, g = nhwc(rng.randn(N, K, H, W)), nhwc(rng.randn(N, K, H, W))
+    po, k12 = bn_params(K, rng), _k12(K, rng)
+    w = torch.as_tensor(rng.randn(K, C).astype(np.float32) * 0.1, device="cuda")
+    xin, pi = nhwc(rng.randn(N, C, H, W)), bn_params(C, rng)
+    res = nhwc(rng.randn(N, C, H, W)) if resid else None
+    l2, st = 0.25, stream_handle()
+    dy0, dx0, dw0 = torch.empty_like(g), torch.empty_like(xin), torch.empty_like(w)
+    assert lib.dk_pwconv_dgrad_bnbwd_f32(g.data_ptr(), xo.data_ptr(), N, H, W, K, *args(po, 1), k12.data_ptr(),
+                                         dy0.data_ptr(), w.data_ptr(), C, dx0.data_ptr(),
+                                         res.data_ptr() if resid else 0, 0, 0, 0, 0, 0, 0, 0, st) == 0
+    nb = lib.dk_pwconv_wgrad_workspace_bytes(N, H, W, K, C)
+    wa = (dy0.data_ptr(), xin.data_ptr(), N, H, W, C, K, 1, H, W, w.data_ptr(), l2, dw0.data_ptr(),
+          workspace.get(nb), nb)
+    assert (lib.dk_pwconv_wgrad_bnx_f32(*wa, *args(pi, 1), st) if bn else lib.dk_pwconv_wgrad_f32(*wa, st)) == 0
+    dx1, dw1 = torch.full_like(xin, float("nan")), torch.full_like(w, float("nan"))
+    nb = lib.dk_pwconv_bwd_fused_workspace_bytes(N, H, W, K, C)
+    assert lib.dk_pwconv_bwd_bnbwd_f32(g.data_ptr(), xo.data_ptr(), N, H, W, K, *args(po, 1), k12.data_ptr(),
+                                       w.data_ptr(), C, l2, dw1.data_ptr(), dx1.data_ptr(),
+                                       res.data_ptr() if resid else 0, xin.data_ptr(),
+                                       *(args(pi, 1) if bn else (0, 0, 0, 0, 0)), 0, workspace.get(nb), nb, st) == 0
+    torch.cuda.synchronize()
+    same(dx0, dx1)
+    err = float((dw1 - dw0).norm() / dw0.norm())
+    assert err < 2e-6, err
+
+
 def test_network_step_with_fused_pw_backward(monkeypatch):
     """The layer path (DORKNET_PW_FUSED_BWD=1) in a full ResNet training step: every parameter
     gradient matches the default (unfused) path to fp32 rounding."""

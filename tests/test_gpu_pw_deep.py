@@ -41,6 +41,7 @@ def _modes(fn):
 
 
 def _close_sums(p0, p1):
+    assert torch.isfinite(p0).all() and torch.isfinite(p1).all()  # every queried row was written
     s0, s1 = p0.sum(0), p1.sum(0)
     return float((s1 - s0).norm() / max(float(s0.norm()), 1e-300)) < 1e-12
 
@@ -373,3 +374,34 @@ def test_deep_plain_dgrad_matches_tiled_engine(K, C, N, H, W):
     assert torch.equal(d0, d1)
     ref = dy.permute(0, 2, 3, 1).reshape(M, K).double() @ w.double()
     assert float((d1.double().reshape(M, C) - ref).norm() / ref.norm()) < 1e-5
+
+
+# fwd_kernel<KR, BN, STATS, STRIDED, HB> forms the cases above reach: the (bn, stats, stride, bias) of
+# test_deep_fwd_matches_tiled_engine at every KR, and the plain strided form of
+# test_deep_strided_skip_projection at KR = 64, 128, 256
+_FWD_REACHED = {(True, True, False, False), (True, True, True, False), (False, True, False, True),
+                (True, False, False, False), (False, False, True, True)}
+_FWD_UNREACHED = [(C, bn, stats, strided, bias) for C in (64, 128, 256, 512) for bn in (False, True)
+                  for stats in (False, True) for strided in (False, True) for bias in (False, True)
+                  if (bn, stats, strided, bias) not in _FWD_REACHED
+                  and not ((bn, stats, strided, bias) == (False, False, True, False) and C != 512)]
+
+
+@pytest.mark.parametrize("C,bn,stats,strided,bias", _FWD_UNREACHED)
+def test_every_launch_form_at_small_shapes(C, bn, stats, strided, bias):
+    """The fwd_kernel forms that no case above reaches (41 of the 64), at 2 x 5 x 7 = 70 output pixels
+    (a ragged last tile, three tiles per column group) and K = 256 (two column groups)."""
+    H, W = (9, 13) if strided else (5, 7)
+    test_deep_fwd_matches_tiled_engine(256, C, bn, 1, stats, 2 if strided else 1, bias, 2, H, W)
+
+
+@pytest.mark.parametrize("bn_in,resid", [(False, False), (True, False), (False, True), (True, True)])
+def test_every_launch_form_at_small_shapes_dgrad(bn_in, resid):
+    """dgrad_kernel<64, RES, PART>: no shape above has the reduction K = 64 (K = 64, C = 128: the
+    28 x 28 units' first pointwise layer)."""
+    test_deep_dgrad_bnbwd_matches_tiled_engine(64, 128, 1, bn_in, resid, 2, 5, 7)
+
+
+def test_every_launch_form_at_small_shapes_plain():
+    """dgrad_kernel<64, false, false, PLAIN>."""
+    test_deep_plain_dgrad_matches_tiled_engine(64, 128, 2, 5, 7)

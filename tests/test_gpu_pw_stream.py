@@ -104,8 +104,19 @@ def test_stream_fwd_ex_matches_tiled_engine(bn, relu, stats, stride, bias, N, H,
     (y0, p0, r0), (y1, p1, r1) = outs
     assert torch.equal(y0, y1)
     if stats:
+        assert torch.isfinite(p0).all() and torch.isfinite(p1).all()  # every queried row was written
         s0, s1 = p0.sum(0), p1.sum(0)
         assert float((s1 - s0).norm() / s0.norm()) < 1e-12
+
+
+@pytest.mark.parametrize("KC", [64, 128])
+@pytest.mark.parametrize("bn,stats,stride", [(True, False, 2), (False, True, 2), (False, False, 1)])
+def test_every_launch_form_at_small_shapes(bn, stats, stride, KC):
+    """The fwd_kernel forms (BN, STATS, STRIDED) that no case above reaches, at 2 x 5 x 7 = 70 output
+    pixels: a ragged last 32-pixel tile, three tiles.  (Every dgrad_bnbwd_kernel form is reached above,
+    the bwd_fused_kernel forms in test_gpu_pw_bwd_fused.py and test_gpu_pw_lattice_fused.py.)"""
+    H, W = (5, 7) if stride == 1 else (9, 13)
+    test_stream_fwd_ex_matches_tiled_engine(bn, 1, stats, stride, False, 2, H, W, KC)
 
 
 def carve(shape, rng, tail=4096, fill=None):

@@ -53,7 +53,7 @@ def test_bf16_stream_fwd_matches_tiled_engine(K, C, bn, relu, stats, bias, N, H,
         try:
             y, ybuf = padded(M, K)
             rows = lib.dk_pwconv_fwd_bf16_stats_rows(N, H, W, K, C)
-            part = torch.zeros((rows, 2, K), dtype=torch.float64, device="cuda") if stats else None
+            part = torch.full((rows, 2, K), float("nan"), dtype=torch.float64, device="cuda") if stats else None
             bn_args = (*(t.data_ptr() for t in p), relu) if bn else (0, 0, 0, 0, 0)
             assert lib.dk_pwconv_fwd_ex_bf16(x.data_ptr(), N, H, W, C, w.data_ptr(), K, 1,
                                              b.data_ptr() if bias else 0, y.data_ptr(), H, W, *bn_args,
@@ -71,6 +71,7 @@ def test_bf16_stream_fwd_matches_tiled_engine(K, C, bn, relu, stats, bias, N, H,
         # at most one partial row per persistent block (a 32-pixel tile each at the least: the
         # weight-stationary kernels' walkers), against one per 64-pixel tile for the tiled engine
         assert rows1 <= max(rows0, -(-M // 32), 1)
+        assert torch.isfinite(part0).all() and torch.isfinite(part1).all()  # every queried row was written
         s0, s1 = part0.sum(0), part1.sum(0)
         assert float((s1 - s0).norm() / s0.norm()) < 1e-12
 
@@ -237,3 +238,19 @@ def test_bf16_fused_bwd_matches_dgrad_and_fp64(K, C, relu, bn_in, resid, N, H, W
     bound = 3e-5 * (dy64.abs().t() @ xh.abs()) + 1e-6
     assert bool(torch.isfinite(dw).all())
     assert bool(((dw.double() - ref).abs() <= bound).all()), float(((dw.double() - ref).abs() / bound).max())
+
+
+# The forms no case above reaches, at 2 x 5 x 7 = 70 pixels (a ragged last 32-pixel tile, three
+# tiles).  Streaming fwd_kernel<KR, NO, BN, STATS>: neither BN nor statistics.  Deep
+# fwd_kernel<KR, BN, STATS, HB>: the cases above reach (1, 1, 0), (0, 1, 1) and (1, 0, 0).  Every
+# form of the dgrad and fused-backward kernels, streaming and deep, is reached above.
+@pytest.mark.parametrize("K,C", [(64, 64), (128, 64), (64, 128), (128, 128)])
+def test_every_launch_form_at_small_shapes(K, C):
+    test_bf16_stream_fwd_matches_tiled_engine(K, C, False, 0, False, False, 2, 5, 7)
+
+
+@pytest.mark.parametrize("C", [128, 256, 512])
+@pytest.mark.parametrize("bn,stats,bias", [(False, False, False), (False, False, True), (False, True, False),
+                                           (True, False, True), (True, True, True)])
+def test_every_launch_form_at_small_shapes_deep(C, bn, stats, bias, deep16):
+    test_bf16_stream_fwd_matches_tiled_engine(256, C, bn, 1, stats, bias, 2, 5, 7)

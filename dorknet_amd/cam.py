@@ -8,6 +8,8 @@ requested classes in one HIP launch (dk_cam_f32 / dk_cam_bf16 in dorknet_amd/csr
 per map), and the arg-sort that picks the classes in another (dk_topk_rows_f32).
 
 - ``top_classes(scores, k=3)``: ``np.argsort(scores)[::-1][:k]`` per row, as an int32 (N, k) device tensor.
+- ``top_classes_with_scores(scores, k=5)``: the same indices and the scores at them (dk_topk_rows_vals_f32;
+  ``FeedForwardNetwork.predict``).
 - ``class_activation_maps(features, dense_weights, class_idx, images=None, out_size=None, shift=128.0,
   want_masks=True)`` -> ``(masks | None, overlays | None)``: fp32 (N, K, H, W) masks (the reference's
   ``cam_img``) and uint8 (N, K, H, W, 3) BGR overlays, both on the GPU.
@@ -43,6 +45,24 @@ def top_classes(scores, k=3) -> torch.Tensor:
     out = torch.empty((n, k), dtype=torch.int32, device=s.device)
     lib.dk_topk_rows_f32(s.data_ptr(), n, classes, k, out.data_ptr(), stream_handle())
     return out
+
+
+def top_classes_with_scores(scores, k=5):
+    """``top_classes`` plus the k scores themselves (dk_topk_rows_vals_f32): (int32 (N, k), fp32 (N, k)),
+    both on the GPU, ``values == scores.gather(1, idx)``."""
+    if not isinstance(scores, torch.Tensor) or scores.dim() != 2:
+        raise ValueError("scores must be a 2-D (N, classes) tensor, got {}".format(
+            tuple(scores.shape) if hasattr(scores, "shape") else type(scores)))
+    n, classes = scores.shape
+    k = int(k)
+    if n < 1 or not 1 <= k <= min(classes, MAX_TOP):
+        raise ValueError("top_classes_with_scores needs N >= 1 and 1 <= k <= min(classes, {}), got N = {}, "
+                         "classes = {}, k = {}".format(MAX_TOP, n, classes, k))
+    s = scores.to(device="cuda", dtype=F32).contiguous()
+    idx = torch.empty((n, k), dtype=torch.int32, device=s.device)
+    val = torch.empty((n, k), dtype=F32, device=s.device)
+    lib.dk_topk_rows_vals_f32(s.data_ptr(), n, classes, k, idx.data_ptr(), val.data_ptr(), stream_handle())
+    return idx, val
 
 
 def class_activation_maps(features, dense_weights, class_idx, images=None, out_size=None, shift=128.0,

@@ -238,7 +238,7 @@ __global__ __launch_bounds__(kCamThreads) void cam_kernel(const T* __restrict__ 
 __device__ __forceinline__ bool topk_better(float v, int i, float bv, int bi) { return v > bv || (v == bv && i > bi); }
 
 __global__ __launch_bounds__(256) void topk_rows_kernel(const float* __restrict__ scores, int classes, int K,
-                                                        int* __restrict__ idx_out) {
+                                                        int* __restrict__ idx_out, float* __restrict__ val_out) {
   __shared__ float rv[4];
   __shared__ int ri[4];
   __shared__ int taken[16];
@@ -279,6 +279,7 @@ __global__ __launch_bounds__(256) void topk_rows_kernel(const float* __restrict_
       bi = max(bi, 0);   // only NaN scores leave no winner; the index stays inside the row
       taken[r] = bi;
       idx_out[(size_t)blockIdx.x * K + r] = bi;
+      if (val_out) val_out[(size_t)blockIdx.x * K + r] = row[bi];   // dk_topk_rows_vals_f32: the score itself
     }
     __syncthreads();
   }
@@ -320,6 +321,15 @@ DK_API int dk_cam_bf16(const uint16_t* feat, int N, int h, int w, int C, const f
 
 DK_API int dk_topk_rows_f32(const float* scores, int N, int classes, int K, int* idx_out, void* stream) {
   if (!scores || !idx_out || N < 1 || classes < 1 || K < 1 || K > 16 || K > classes) return DK_ERR_ARGS;
-  hipLaunchKernelGGL(topk_rows_kernel, dim3((unsigned)N), dim3(256), 0, as_stream(stream), scores, classes, K, idx_out);
+  hipLaunchKernelGGL(topk_rows_kernel, dim3((unsigned)N), dim3(256), 0, as_stream(stream), scores, classes, K, idx_out,
+                     (float*)nullptr);
+  return launch_status();
+}
+
+DK_API int dk_topk_rows_vals_f32(const float* scores, int N, int classes, int K, int* idx_out, float* val_out,
+                                 void* stream) {
+  if (!scores || !idx_out || !val_out || N < 1 || classes < 1 || K < 1 || K > 16 || K > classes) return DK_ERR_ARGS;
+  hipLaunchKernelGGL(topk_rows_kernel, dim3((unsigned)N), dim3(256), 0, as_stream(stream), scores, classes, K, idx_out,
+                     val_out);
   return launch_status();
 }

@@ -3,7 +3,8 @@
 Same API: ``add_layer``, ``set_loss_layer``, ``to_gpu``, ``forward(X, y_one_hot,
 test_mode=False, terminal_layer_name=None) -> (loss, X)``, ``backward()``, ``test``,
 ``save_weights_to_h5``, ``save_layer_structure_to_json``,
-``load_network_from_json_and_h5``.  The forward pass runs (BatchNormLayer, ReLu) pairs
+``load_network_from_json_and_h5``; beside ``test``, ``evaluate`` and ``predict`` keep the
+counting and the arg-sort on the device (dorknet_amd/metrics.py).  The forward pass runs (BatchNormLayer, ReLu) pairs
 fused (layers/_chain.py) and remembers the steps it took for ``backward``.
 """
 from __future__ import annotations
@@ -173,6 +174,57 @@ class FeedForwardNetwork:
             test_correct_total += np.sum(np.asarray(y_test_batch) ==
                                          np.argmax(batch_scores.cpu().numpy(), axis=1))
         return float(test_correct_total) / test_set_size
+
+    def evaluate(self, data_loader, top=(1, 5), confusion=False, num_batches=None):
+        """Accuracy, top-k accuracy, loss and (confusion=True) the confusion matrix over the (X, y, _)
+        triples of `data_loader`, the loader that `test` takes: X host or device, fp32 or bf16, y the
+        integer labels (a list, an array or a tensor), batches of any sizes.  Per batch: as_device,
+        forward(X, None, test_mode=True) and one counter launch (dorknet_amd/metrics.py; DESIGN.md
+        section 16); nothing comes back to the host before the final read.  Returns a
+        ClassificationReport; `top` lists the k (1 <= k <= min(classes, 16)) its repr prints;
+        num_batches stops after that many batches.  A label outside [0, classes) leaves its row out."""
+        from ..metrics import RANK_BINS, ClassificationMeter
+        try:
+            top = tuple(int(k) for k in ((top,) if np.isscalar(top) else top))
+        except (TypeError, ValueError):
+            raise ValueError("evaluate: top must be integers, got {!r}".format(top))
+        if not top or min(top) < 1 or max(top) > RANK_BINS:
+            raise ValueError("evaluate: top needs 1 <= k <= min(classes, {}), got {}".format(RANK_BINS, top))
+        if num_batches is not None and int(num_batches) < 1:
+            raise ValueError("evaluate: num_batches must be at least 1, got {}".format(num_batches))
+        if self.loss_layer is None:
+            raise ValueError("evaluate: the network has no loss layer, so no scores to evaluate")
+        meter = None
+        for i, (X, y, _) in enumerate(data_loader):
+            if num_batches is not None and i >= int(num_batches):
+                break
+            _, scores = self.forward(as_device(X, act_dtype(X)), None, test_mode=True)
+            if meter is None:
+                classes = scores.shape[1]
+                if max(top) > classes:
+                    raise ValueError("evaluate: top needs 1 <= k <= min(classes, {}), got {} for {} classes".format(
+                        RANK_BINS, top, classes))
+                meter = ClassificationMeter(classes, confusion=confusion)
+            meter.update(scores, y)
+        if meter is None:
+            raise ValueError("evaluate: the data loader gave no batch")
+        return meter.result(top)
+
+    def predict(self, X, top=5):
+        """The `top` best classes of every image of the batch X and their scores, best first:
+        (class_idx int32 (N, top), scores fp32 (N, top)), both on the GPU -- the
+        ``np.argsort(scores)[::-1]`` loop of the reference's
+        examples/imagenet_dogs_225_resnet_18_depsep_evaluate.py:41-46 for a whole batch
+        (dk_topk_rows_vals_f32).  1 <= top <= min(classes, 16)."""
+        from ..cam import MAX_TOP, top_classes_with_scores
+        if isinstance(top, bool) or not isinstance(top, (int, np.integer)) or not 1 <= top <= MAX_TOP:
+            raise ValueError("predict: top must be an integer with 1 <= top <= min(classes, {}), got {!r}".format(
+                MAX_TOP, top))
+        if not hasattr(X, "shape") or len(X.shape) < 2 or X.shape[0] < 1:
+            raise ValueError("predict: X must be a batch (N >= 1, ...) array or tensor, got {}".format(
+                tuple(X.shape) if hasattr(X, "shape") else type(X)))
+        _, scores = self.forward(as_device(X, act_dtype(X)), None, test_mode=True)
+        return top_classes_with_scores(scores, int(top))
 
     def class_activation_maps(self, X, top=3, feature_layer="res8", dense_layer="dense1", feature_test_mode=True):
         """Class activation maps of the `top` best classes of every image of the batch X (fp32 or bf16

@@ -607,6 +607,43 @@ int dk_nhwc_unpad_f32(const float* x, long long P, int Cp, int C, float* y, void
 int dk_cam_f32(const float* feat, int N, int h, int w, int C, const float* weights, int classes, const int* class_idx, int K, const float* image, int H, int W, float shift, float* mask, uint8_t* overlay, void* stream);
 int dk_cam_bf16(const uint16_t* feat, int N, int h, int w, int C, const float* weights, int classes, const int* class_idx, int K, const float* image, int H, int W, float shift, float* mask, uint8_t* overlay, void* stream);
 int dk_topk_rows_f32(const float* scores, int N, int classes, int K, int* idx_out, void* stream);
+/* dk_topk_rows_vals_f32: dk_topk_rows_f32 plus the K scores themselves, val_out fp32 [N][K] with
+ * val_out[b][r] = scores[b][idx_out[b][r]]; the same kernel, the same indices, the same argument errors
+ * (a NULL val_out included). */
+int dk_topk_rows_vals_f32(const float* scores, int N, int classes, int K, int* idx_out, float* val_out, void* stream);
+
+/* ---------------------------------------------------------------------------------------
+ * Evaluation counters (dorknet_amd/csrc/metrics.hip): one launch per batch adds a
+ * batch's accuracy, top-k, confusion and loss counts to device-resident int64 words, so a validation run
+ * goes to the host once (the reference's FeedForwardNetwork.test copies every batch's scores).  Pinned
+ * by tests/_metrics_ref.py.
+ *   scores     fp32 [N][classes] row-major: what forward(X, None, test_mode=True) returns; any fp32 matrix;
+ *   labels     device int32 [N]; a label outside [0, classes) makes its row *ignored*;
+ *   state      int64 [DK_CLASSIFY_STATE_WORDS], added to, never overwritten (zero it to start):
+ *              [0] rows counted n   [1] rows ignored   [2] rows with pred == y   [3] non-finite rows
+ *              [4] sum over finite rows of llrint((double)nll * 2^32): the loss in Q32 fixed point
+ *              [5 + r], r = 0..15: rows with rank == r   [21] rows with rank >= 16;
+ *   confusion  int64 [classes][classes] or NULL: confusion[y][pred] += 1 per counted row;
+ *   pred_out, rank_out (int32 [N]), nll_out (fp32 [N]): the per-row values, each or NULL.
+ * Per row with label y and scores s:
+ *   pred = np.argmax(s): of equal maxima the LOWEST index (the rule of FeedForwardNetwork.test);
+ *   rank = #{j : s[j] > s[y]} + #{j > y : s[j] == s[y]}, the position of y in
+ *          np.argsort(s, kind="stable")[::-1]: rank < k exactly when y is among dk_topk_rows_f32's first
+ *          k (of equal scores the HIGHER index first).  pred == y and rank == 0 differ only on a row
+ *          whose maximum is tied; both rules are the reference's (test, and its evaluate program);
+ *   nll  = -logf(s[y]), bit-identical to dk_softmax_xent_fwd_f32's per-row term for a one-hot label.
+ * An ignored row adds 1 to state[1] and to nothing else; it writes rank = -1, nll = 0 and its pred.  A
+ * row whose nll is not finite (s[y] zero, negative, NaN or infinite) counts in state[3] and adds nothing
+ * to state[4]; it counts everywhere else.  NaN scores give unspecified pred and rank inside [0, classes);
+ * nothing is indexed out of range.
+ * All counters are integers, so the adds commute: workgroups combine through LDS and one atomic per word,
+ * and two runs give the same bits; merging two states is an integer vector add.  An fp32 nll >= 2^-9
+ * times 2^32 is an integer and is carried exactly; below that a row is off by at most 2^-33.  Capacity:
+ * 2^63 / (103.3 * 2^32), about 2.0e7 rows of the worst finite fp32 case (s[y] = 2^-149), or 4e8 rows at
+ * a loss of 5.
+ * 10001, and nothing is launched, for N < 1, classes < 2 (or > 2^31 - 1025), a NULL scores, labels or state. */
+#define DK_CLASSIFY_STATE_WORDS 22
+int dk_classify_accumulate_f32(const float* scores, const int* labels, int N, int classes, long long* state, long long* confusion, int* pred_out, int* rank_out, float* nll_out, void* stream);
 
 #ifdef __cplusplus
 }

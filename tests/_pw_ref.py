@@ -249,9 +249,9 @@ def _sum(a):
     return np.asarray(a, dtype=np.longdouble).sum(axis=0).astype(np.float64)
 
 
-def stats_checks(name, stats, stored, ref, bound):
+def stats_checks(name, stats, stored, ref, bound, check=check):
     """stats[rows][2][K] against (1) the fp64 sums of the stored y and (2) the fp64 reference sums.
-    stored / ref / bound: (N,K,OH,OW)."""
+    stored / ref / bound: (N,K,OH,OW).  check: the family's check (its log tag; tests/_conv_ref.py passes its own)."""
     stats = np.asarray(stats, dtype=np.float64)
     assert not np.isnan(stats).any(), "{}: partial rows never written".format(name)
     got = _sum(stats)

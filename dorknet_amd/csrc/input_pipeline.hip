@@ -299,6 +299,133 @@ __global__ __launch_bounds__(256) void augment_u8_kernel(const uint8_t* __restri
   }
 }
 
+// Device-resident image store: decoded uint8 HWC images of differing sizes back
+// to back in one buffer, one record per image; a batch is an int32 table of (image, crop row, crop col).
+// store_pixel is the one source-pixel function of every store entry: the pixel at (crop_row + oy,
+// crop_col + ox) of that image resized to TH x TW -- what resize_linear_u8_kernel followed by the crop
+// gives, computed for the crop window only.  The resize mode is per image: blockIdx.y is the image, so a
+// block never diverges on it.
+struct StoreImage {   // = dk_store_image
+  long long offset;   // bytes from the start of the store
+  int H, W;
+};
+static_assert(sizeof(StoreImage) == sizeof(dk_store_image), "store record layout");
+
+struct Px4 {
+  int v[4];   // channels past C are 0
+};
+
+__device__ __forceinline__ Px4 store_pixel(const uint8_t* __restrict__ data, const StoreImage* __restrict__ images,
+                                           int count, int C, const int* __restrict__ rec, int TH, int TW, int OH,
+                                           int OW, int oy, int ox) {
+  // a bad table cannot read out of bounds: the image index and the crop offsets are clamped
+  const StoreImage im = images[min(max(rec[0], 0), count - 1)];
+  const int y = min(max(rec[1], 0), TH - OH) + oy, x = min(max(rec[2], 0), TW - OW) + ox;
+  const int H = im.H, W = im.W;
+  const uint8_t* src = data + im.offset;   // 64-bit: the store is meant to exceed 4 GB
+  const size_t pitch = (size_t)W * C;
+  Px4 o = {{0, 0, 0, 0}};
+  if (H == TH && W == TW) {  // copy
+    const uint8_t* p = src + (size_t)y * pitch + (size_t)x * C;
+#pragma unroll
+    for (int c = 0; c < 4; ++c)
+      if (c < C) o.v[c] = p[c];
+  } else if (H == 2 * TH && W == 2 * TW) {  // INTER_AREA for the exact 2x downscale of both axes
+    const uint8_t* p = src + (size_t)(2 * y) * pitch + (size_t)(2 * x) * C;
+    const uint8_t* q = p + pitch;
+#pragma unroll
+    for (int c = 0; c < 4; ++c)
+      if (c < C) o.v[c] = (p[c] + p[C + c] + q[c] + q[C + c] + 2) >> 2;
+  } else {
+    // cv::resize: inv_scale = dsize / ssize, scale = 1 / inv_scale, from this image's own size
+    const double scy = 1.0 / ((double)TH / (double)H), scx = 1.0 / ((double)TW / (double)W);
+    const CvAxis ax = cv_axis_x(x, scx, W), ay = cv_axis_y(y, scy, H);
+    const uint8_t* r0 = src + (size_t)ay.s0 * pitch;
+    const uint8_t* r1 = src + (size_t)ay.s1 * pitch;
+    const size_t x0 = (size_t)ax.s0 * C, x1 = (size_t)ax.s1 * C;
+#pragma unroll
+    for (int c = 0; c < 4; ++c)
+      if (c < C) {
+        const int S0 = r0[x0 + c] * ax.a0 + r0[x1 + c] * ax.a1;
+        const int S1 = r1[x0 + c] * ax.a0 + r1[x1 + c] * ax.a1;
+        o.v[c] = min(max((S0 * ay.a0 + S1 * ay.a1 + (1 << 21)) >> 22, 0), 255);
+      }
+  }
+  return o;
+}
+
+// OUT 0: uint8 NHWC [N][OH][OW][C] (the cropped image, for the augmenter); 1: fp32 NCHW [N][C][OH][OW];
+// 2: bf16 channels-last [N][OH][OW][C], round-to-nearest-even of the fp32 value.  OUT 1 / 2: pixel - shift;
+// with a partner table also the partner image's value xm, ab = p * xm + q * x and ba = p * x + q * xm,
+// every product and sum rounded on its own as in mixup_kernel.  One thread per output pixel, all channels.
+template <int OUT>
+__global__ __launch_bounds__(256) void store_batch_kernel(const uint8_t* __restrict__ data,
+                                                          const StoreImage* __restrict__ images, int count, int C,
+                                                          const int* __restrict__ batch,
+                                                          const int* __restrict__ partner, int N, int TH, int TW,
+                                                          int OH, int OW, float shift, float p, float q,
+                                                          void* __restrict__ ab, void* __restrict__ ba) {
+  const int n = blockIdx.y;
+  const int i = blockIdx.x * 256 + threadIdx.x;  // over OH * OW (< 2^31 - 256: the entry points check)
+  if (n >= N || i >= OH * OW) return;
+  const int ox = i % OW, oy = i / OW;
+  const Px4 a = store_pixel(data, images, count, C, batch + 3 * (size_t)n, TH, TW, OH, OW, oy, ox);
+  if constexpr (OUT == 0) {
+    uint8_t* out = (uint8_t*)ab + ((size_t)n * OH * OW + i) * C;
+#pragma unroll
+    for (int c = 0; c < 4; ++c)
+      if (c < C) out[c] = (uint8_t)a.v[c];
+  } else {
+    float x[4], y[4];
+#pragma unroll
+    for (int c = 0; c < 4; ++c) x[c] = __fsub_rn((float)a.v[c], shift);
+    const bool mix = partner != nullptr;
+    if (mix) {
+      const Px4 b = store_pixel(data, images, count, C, partner + 3 * (size_t)n, TH, TW, OH, OW, oy, ox);
+#pragma unroll
+      for (int c = 0; c < 4; ++c) {
+        const float xm = __fsub_rn((float)b.v[c], shift);
+        y[c] = __fadd_rn(__fmul_rn(p, x[c]), __fmul_rn(q, xm));   // p * X + (1 - p) * X_m
+        x[c] = __fadd_rn(__fmul_rn(p, xm), __fmul_rn(q, x[c]));   // p * X_m + (1 - p) * X
+      }
+    }
+    const size_t plane = (size_t)OH * OW;
+    const size_t e = OUT == 1 ? (size_t)n * C * plane + i : ((size_t)n * plane + i) * C;
+    const size_t step = OUT == 1 ? plane : 1;
+#pragma unroll
+    for (int c = 0; c < 4; ++c)
+      if (c < C) {
+        if constexpr (OUT == 1) {
+          ((float*)ab)[e + c * step] = x[c];
+          if (mix) ((float*)ba)[e + c * step] = y[c];
+        } else {
+          st1((bf16_t*)ab + e + c * step, x[c]);
+          if (mix) st1((bf16_t*)ba + e + c * step, y[c]);
+        }
+      }
+  }
+}
+
+// One-hot rows of a batch's labels, mixed with the partner batch's as the images are:
+// y_ab[n][c] = p * [c == lm] + q * [c == l] and its mirror; without a partner the plain one-hot row.
+// A label outside [0, classes) matches no column: a zero row.
+__global__ void onehot_mixup_kernel(const int* __restrict__ labels, const int* __restrict__ partner, long long total,
+                                    int classes, float p, float q, float* __restrict__ y_ab,
+                                    float* __restrict__ y_ba) {
+  const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;  // over N * classes
+  if (i >= total) return;
+  const int c = (int)(i % classes);
+  const long long n = i / classes;
+  const float e = labels[n] == c ? 1.f : 0.f;
+  if (!partner) {
+    y_ab[i] = e;
+    return;
+  }
+  const float em = partner[n] == c ? 1.f : 0.f;
+  y_ab[i] = __fadd_rn(__fmul_rn(p, em), __fmul_rn(q, e));
+  y_ba[i] = __fadd_rn(__fmul_rn(p, e), __fmul_rn(q, em));
+}
+
 }  // namespace dk
 
 using namespace dk;
@@ -368,4 +495,61 @@ DK_API int dk_augment_u8_to_nchw_f32(const uint8_t* src, int N, int H, int W, in
                                      const dk_augment_params* params, float shift, float* dst, void* stream) {
   if (!augment_args_ok(src, N, H, W, C, OH, OW, params, dst)) return DK_ERR_ARGS;
   return launch_augment<true>(src, N, H, W, crop_rc, OH, OW, params, shift, dst, stream);
+}
+
+static inline bool store_args_ok(const void* data, const void* images, int count, int C, const void* batch, int N,
+                                 int TH, int TW, int OH, int OW, const void* dst) {
+  return data && images && batch && dst && count >= 1 && N >= 1 && C >= 1 && C <= 4 && OH >= 1 && OW >= 1 &&
+         OH <= TH && OW <= TW && (long long)OH * OW <= 0x7fffffffLL - 256;  // the kernel's 32-bit pixel index
+}
+
+// grid.y is the output image (at most 65535 per launch: larger batches take several launches)
+template <int OUT>
+static int launch_store(const uint8_t* data, const dk_store_image* images, int count, int C, const int* batch,
+                        const int* partner, int N, int TH, int TW, int OH, int OW, float shift, float p, float q,
+                        void* ab, void* ba, void* stream) {
+  const int kMaxY = 65535;
+  const size_t out_image = (size_t)OH * OW * C * (OUT == 1 ? sizeof(float) : OUT == 2 ? sizeof(bf16_t) : 1);
+  for (int n0 = 0; n0 < N; n0 += kMaxY) {
+    const int nb = N - n0 < kMaxY ? N - n0 : kMaxY;
+    hipLaunchKernelGGL(store_batch_kernel<OUT>, dim3(blocks256((long long)OH * OW), nb), dim3(256), 0,
+                       as_stream(stream), data, reinterpret_cast<const StoreImage*>(images), count, C,
+                       batch + 3 * (size_t)n0, partner ? partner + 3 * (size_t)n0 : nullptr, nb, TH, TW, OH, OW, shift,
+                       p, q, (void*)((uint8_t*)ab + (size_t)n0 * out_image),
+                       ba ? (void*)((uint8_t*)ba + (size_t)n0 * out_image) : nullptr);
+  }
+  return launch_status();
+}
+
+DK_API int dk_store_crop_u8(const uint8_t* data, const dk_store_image* images, int count, int C, const int* batch,
+                            int N, int TH, int TW, int OH, int OW, uint8_t* dst, void* stream) {
+  if (!store_args_ok(data, images, count, C, batch, N, TH, TW, OH, OW, dst)) return DK_ERR_ARGS;
+  return launch_store<0>(data, images, count, C, batch, nullptr, N, TH, TW, OH, OW, 0.f, 0.f, 0.f, dst, nullptr,
+                         stream);
+}
+
+DK_API int dk_store_batch_nchw_f32(const uint8_t* data, const dk_store_image* images, int count, int C,
+                                   const int* batch, const int* partner, int N, int TH, int TW, int OH, int OW,
+                                   float shift, float p, float one_minus_p, float* ab, float* ba, void* stream) {
+  if (!store_args_ok(data, images, count, C, batch, N, TH, TW, OH, OW, ab) || (partner && !ba)) return DK_ERR_ARGS;
+  return launch_store<1>(data, images, count, C, batch, partner, N, TH, TW, OH, OW, shift, p, one_minus_p, ab,
+                         partner ? ba : nullptr, stream);
+}
+
+DK_API int dk_store_batch_nhwc_bf16(const uint8_t* data, const dk_store_image* images, int count, int C,
+                                    const int* batch, const int* partner, int N, int TH, int TW, int OH, int OW,
+                                    float shift, float p, float one_minus_p, uint16_t* ab, uint16_t* ba,
+                                    void* stream) {
+  if (!store_args_ok(data, images, count, C, batch, N, TH, TW, OH, OW, ab) || (partner && !ba)) return DK_ERR_ARGS;
+  return launch_store<2>(data, images, count, C, batch, partner, N, TH, TW, OH, OW, shift, p, one_minus_p, ab,
+                         partner ? ba : nullptr, stream);
+}
+
+DK_API int dk_onehot_mixup_f32(const int* labels, const int* partner, int N, int classes, float p, float one_minus_p,
+                               float* y_ab, float* y_ba, void* stream) {
+  if (!labels || !y_ab || N < 1 || classes < 1 || (partner && !y_ba)) return DK_ERR_ARGS;
+  const long long total = (long long)N * classes;
+  hipLaunchKernelGGL(onehot_mixup_kernel, dim3(blocks256(total)), dim3(256), 0, as_stream(stream), labels, partner,
+                     total, classes, p, one_minus_p, y_ab, y_ba);
+  return launch_status();
 }

@@ -171,6 +171,8 @@ class FeedForwardNetwork:
         for X_test_batch, y_test_batch, _ in tqdm(data_loader, total=test_set_size / batch_size):
             X_test_batch = as_device(X_test_batch)
             _, batch_scores = self.forward(X_test_batch, y_one_hot=None, test_mode=True)
+            if hasattr(y_test_batch, "cpu"):  # labels on the device (DeviceImageDataLoader)
+                y_test_batch = y_test_batch.cpu().numpy()
             test_correct_total += np.sum(np.asarray(y_test_batch) ==
                                          np.argmax(batch_scores.cpu().numpy(), axis=1))
         return float(test_correct_total) / test_set_size

@@ -73,6 +73,38 @@ typedef struct dk_augment_params {
 int dk_augment_u8(const uint8_t* src, int N, int H, int W, int C, const int* crop_rc, int OH, int OW, const dk_augment_params* params, uint8_t* dst, void* stream);
 int dk_augment_u8_to_nchw_f32(const uint8_t* src, int N, int H, int W, int C, const int* crop_rc, int OH, int OW, const dk_augment_params* params, float shift, float* dst, void* stream);
 
+/* Device-resident image store and its batch entries, replacing the host loader
+ * data_loading/image_data_loader.py:88-117 around the per-image work above: decoded uint8 HWC images of
+ * differing sizes lie back to back in one device buffer `data` (C channels each, 1 <= C <= 4), `images`
+ * is a device array of `count` records (byte offset into data, 64-bit; H, W >= 1).  A batch is a device
+ * int32 table [N][3] of (image index, crop row, crop col); the index is clamped into [0, count - 1] and
+ * the offsets into [0, TH - OH] x [0, TW - OW], so a bad table cannot read out of bounds.  Output pixel
+ * (oy, ox) of image n is the pixel (crop row + oy, crop col + ox) of that image resized to TH x TW from
+ * its own size exactly as dk_resize_bilinear_u8 resizes it (copy, 2x2 area or 11-bit linear, chosen per
+ * image) -- only the crop window is computed.
+ *  - dk_store_crop_u8: dst uint8 NHWC [N][OH][OW][C] (what the augmenter takes);
+ *  - dk_store_batch_nchw_f32: x = (float)pixel - shift to ab, fp32 NCHW [N][C][OH][OW].  With `partner`
+ *    (a second batch table; NULL: none) xm is the partner image's value, ab = p*xm + (1-p)*x and
+ *    ba = p*x + (1-p)*xm, each product and sum rounded on its own as dk_mixup_f32 does (p and 1-p are
+ *    passed as the fp32 values numpy multiplies by); ba is not written without a partner;
+ *  - dk_store_batch_nhwc_bf16: the same values rounded to nearest even to bf16, channels last
+ *    [N][OH][OW][C] (a torch channels_last tensor of shape (N, C, OH, OW)).
+ * A dense uint8 NHWC batch is a store with offsets n*H*W*C and TH x TW = H x W.
+ *  - dk_onehot_mixup_f32: fp32 rows [N][classes] from int32 labels: y_ab[n][c] = p*[c == partner[n]] +
+ *    (1-p)*[c == labels[n]] and y_ba its mirror, rounded as above; partner NULL: the plain one-hot rows
+ *    to y_ab alone.  A label outside [0, classes) gives a zero row.
+ * NULL data / images / batch / output (ba, y_ba with a partner), count < 1, N < 1, C outside 1..4, classes < 1
+ * or an output window larger than TH x TW: 10001, nothing is launched. */
+typedef struct dk_store_image {
+  long long offset;
+  int H;
+  int W;
+} dk_store_image;
+int dk_store_crop_u8(const uint8_t* data, const dk_store_image* images, int count, int C, const int* batch, int N, int TH, int TW, int OH, int OW, uint8_t* dst, void* stream);
+int dk_store_batch_nchw_f32(const uint8_t* data, const dk_store_image* images, int count, int C, const int* batch, const int* partner, int N, int TH, int TW, int OH, int OW, float shift, float p, float one_minus_p, float* ab, float* ba, void* stream);
+int dk_store_batch_nhwc_bf16(const uint8_t* data, const dk_store_image* images, int count, int C, const int* batch, const int* partner, int N, int TH, int TW, int OH, int OW, float shift, float p, float one_minus_p, uint16_t* ab, uint16_t* ba, void* stream);
+int dk_onehot_mixup_f32(const int* labels, const int* partner, int N, int classes, float p, float one_minus_p, float* y_ab, float* y_ba, void* stream);
+
 /* Path selectors and tuning knobs for tests and A/B runs (dorknet_amd/csrc/knobs.hip: one registry
  * of atomics holding built-in defaults; no environment variable reaches them; not for production
  * use).  cfg = -1 restores the default.  Returns the number of configurations for kinds 0 / 1, 0 for

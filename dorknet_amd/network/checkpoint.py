@@ -292,6 +292,22 @@ def _load_maxpool(layer, open_f, load_grads):
     layer.stride = stride
 
 
+def _save_reshape(layer, open_f, save_grads):
+    """An extension: the reference's ReshapeLayer (layers/reshape.py) has no checkpoint methods.
+    The shapes are stored as they were given, a batch entry of -1 kept."""
+    if layer.input_shape is None:
+        raise ValueError("ReshapeLayer {}: no shapes set, nothing to save".format(layer.layer_name))
+    d = _info(open_f, layer)
+    d.attrs["input_shape"] = np.array(layer.input_shape, dtype=np.int64)
+    d.attrs["output_shape"] = np.array(layer.output_shape, dtype=np.int64)
+
+
+def _load_reshape(layer, open_f, load_grads):
+    a = _attrs(open_f, layer)
+    layer._set_shapes(tuple(int(v) for v in np.asarray(a["input_shape"]).ravel()),
+                      tuple(int(v) for v in np.asarray(a["output_shape"]).ravel()))
+
+
 def _new_layer(l_type, name):
     from ..layers.activations import ReLu
     from ..layers.batch_norm import BatchNormLayer
@@ -301,10 +317,11 @@ def _new_layer(l_type, name):
     from ..layers.losses import SoftmaxWithCrossEntropy
     from ..layers.pointwise_convolution import PointwiseConvLayer
     from ..layers.pooling import GlobalAveragePoolingLayer, MaxPoolLayer
+    from ..layers.reshape import ReshapeLayer
     from ..layers.residual_block import ResidualBlock
     classes = {c.__name__: c for c in (ConvLayer, BatchNormLayer, ReLu, DepthwiseConvLayer, PointwiseConvLayer,
-                                       GlobalAveragePoolingLayer, MaxPoolLayer, DenseLayer, ResidualBlock,
-                                       SoftmaxWithCrossEntropy)}
+                                       GlobalAveragePoolingLayer, MaxPoolLayer, ReshapeLayer, DenseLayer,
+                                       ResidualBlock, SoftmaxWithCrossEntropy)}
     if l_type not in classes:
         raise ValueError("unknown layer type {!r} for layer {!r}".format(l_type, name))
     return classes[l_type](name)
@@ -367,6 +384,7 @@ _HANDLERS = {
     "ReLu": (_save_plain, _load_plain),
     "GlobalAveragePoolingLayer": (_save_plain, _load_plain),
     "MaxPoolLayer": (_save_maxpool, _load_maxpool),
+    "ReshapeLayer": (_save_reshape, _load_reshape),
     "SoftmaxWithCrossEntropy": (_save_plain, _load_plain),
     "ResidualBlock": (_save_residual, _load_residual),
 }

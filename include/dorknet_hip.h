@@ -584,6 +584,22 @@ int dk_maxpool_fwd_bnx_f32(const float* x, int N, int H, int W, int C, int strid
 int dk_maxpool_fwd_bnx_bf16(const uint16_t* x, int N, int H, int W, int C, int stride, const float* bn_mean, const float* bn_invstd, const float* bn_gamma, const float* bn_beta, int bn_relu, uint16_t* y, uint8_t* idx, void* stream);
 int dk_maxpool_bwd_f32(const float* dy, const uint8_t* idx, int N, int H, int W, int C, int stride, float* dx, void* stream);
 int dk_maxpool_bwd_bf16(const uint16_t* dy, const uint8_t* idx, int N, int H, int W, int C, int stride, uint16_t* dx, void* stream);
+/* Flatten / unflatten (layers/reshape.py: X.reshape((B, C*H*W)) on an NCHW array; dorknet_amd/csrc/reshape.hip).
+ * The NHWC side is [N][HW][C], the flat side [N][C*HW] row-major with feature f = c * HW + p: a batched
+ * transpose through LDS, both HBM sides coalesced, every output element written exactly once.
+ *   dk_flatten_fwd_*: NHWC fp32 / bf16 -> flat fp32 (an exact copy / an exact widening).
+ *   dk_flatten_fwd_bnx_*: the same over BN(x) [+ ReLU] formed on load (see *_bnx_*; dk_bn_apply_*'s
+ *     arithmetic, for bf16 rounded to bf16 before it is widened): bit-identical to apply-then-flatten.
+ *   dk_flatten_bwd_*: flat fp32 -> NHWC fp32 (an exact copy) / bf16 (one round-to-nearest-even).
+ * The backward entries are also the forward of an unflatten, the forward entries its backward.
+ * Any C, HW and alignment (4-channel vectors when C % 4 == 0 and the NHWC pointer is aligned for them).
+ * DK_ERR_ARGS: any of N, HW, C below 1, a NULL tensor. */
+int dk_flatten_fwd_f32(const float* x, int N, int HW, int C, float* y, void* stream);
+int dk_flatten_fwd_bf16(const uint16_t* x, int N, int HW, int C, float* y, void* stream);
+int dk_flatten_fwd_bnx_f32(const float* x, int N, int HW, int C, const float* bn_mean, const float* bn_invstd, const float* bn_gamma, const float* bn_beta, int bn_relu, float* y, void* stream);
+int dk_flatten_fwd_bnx_bf16(const uint16_t* x, int N, int HW, int C, const float* bn_mean, const float* bn_invstd, const float* bn_gamma, const float* bn_beta, int bn_relu, float* y, void* stream);
+int dk_flatten_bwd_f32(const float* dy, int N, int HW, int C, float* dx, void* stream);
+int dk_flatten_bwd_bf16(const float* dy, int N, int HW, int C, uint16_t* dx, void* stream);
 int dk_softmax_xent_fwd_f32(const float* x, const float* y_onehot, int B, int K, float* p, float* loss, void* stream);
 int dk_softmax_xent_bwd_f32(const float* p, const float* y_onehot, int B, int K, float* dx, void* stream);
 

@@ -827,7 +827,8 @@ template <class E>
 static int bn_apply_t(const E* x, long long numel, int C, const float* mean, const float* invstd, const float* gamma,
                       const float* beta, int relu, E* y, uint8_t* mask, void* stream) {
   const int P = (int)(numel / C);
-  const bool vec = vec_ok_e(x, C) && vec_ok_e(y, C);
+  // the 4-element route stores a group's mask bytes as one 32-bit word: the mask must be 4-byte aligned for it
+  const bool vec = vec_ok_e(x, C) && vec_ok_e(y, C) && (reinterpret_cast<uintptr_t>(mask) & 3) == 0;
   if (!vec && sizeof(E) != 4) return DK_ERR_ARGS;
   const int V = vec ? 4 : 1;
   const RowGeom g = row_geom(C, V);
@@ -1005,6 +1006,8 @@ static int bn_bwd_t(const E* x, const E* dy, int P, int C, const float* mean, co
                     const float* beta, int relu, float* dgamma, float* dbeta, E* dx, void* ws, size_t ws_bytes,
                     void* stream) {
   if (ws_bytes < dk_bn_bwd_workspace_bytes(P, C)) return DK_ERR_WORKSPACE;
+  // what stage 3 would refuse is refused before stage 1 writes dgamma / dbeta
+  if (sizeof(E) != 4 && !(vec_ok_e(x, C) && vec_ok_e(dy, C) && vec_ok_e(dx, C))) return DK_ERR_ARGS;
   const int nblk = bn_blocks(P, C);
   char* base = static_cast<char*>(ws);
   float* k12 = reinterpret_cast<float*>(base + bn_fold_offset(P, C));

@@ -539,6 +539,8 @@ size_t dk_bn_fold_scratch_bytes(int nrows, int C);
 int dk_bn_fold_tickets_needed_count(int nrows, int nslices);
 int dk_relu_bwd_bn_partial_f64(const float* dy, const uint8_t* mask, const float* x, int P, int C, const float* mean, const float* invstd, const float* gamma, const float* beta, int relu, float* dx, void* part, size_t part_bytes, void* stream);
 int dk_bn_infer_params_f32(const float* run_std, int C, float* invstd, void* stream);
+/* mask (nullable): one byte per element.  The 4-element route needs it 4-byte aligned (as x and y 16-byte, bf16
+ * 8-byte); otherwise fp32 takes the scalar route and bf16 returns DK_ERR_ARGS. */
 int dk_bn_apply_f32(const float* x, long long numel, int C, const float* mean, const float* invstd, const float* gamma, const float* beta, int relu, float* y, uint8_t* mask, void* stream);
 int dk_bn_bwd_partial_f64(const float* x, const float* dy, int P, int C, const float* mean, const float* invstd, const float* gamma, const float* beta, int relu, void* ws, size_t ws_bytes, void* stream);
 int dk_bn_bwd_finalize_f32(const void* part_local, int nblk_local, const void* part_global, int nblk_global, int C, double count, float* dgamma, float* dbeta, float* k12, void* stream);

@@ -1,7 +1,8 @@
 """BN on load (dk_*_bnx_f32, dk_bn_add_f32): a consumer that applies the preceding
 BatchNorm (+ReLU) as it loads its input must produce exactly -- bitwise -- what the
 unfused sequence dk_bn_apply_f32 -> consumer produces (same bn_out arithmetic, padding 0).
-Parity of the unfused sequence itself with the oracle is covered in test_gpu_layers.py."""
+Parity of the unfused sequence itself with the oracle is covered in test_gpu_layers.py, and every element of
+dk_bn_apply_* against an fp64 reference in test_gpu_bn_elementwise.py."""
 import numpy as np
 import pytest
 import torch

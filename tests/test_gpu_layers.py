@@ -184,7 +184,9 @@ def test_dense_layer(case):
     run_layer(layer, rng.randn(B, IN).astype(np.float32), rng.randn(B, OUT).astype(np.float32))
 
 
-@pytest.mark.parametrize("shape", [(3, 16, 5, 7), (2, 64, 9, 9), (4, 6, 3, 3), (5, 24)])
+# the last three: two reduce blocks each, on the float4, the sliced (C / 4 = 257) and the scalar route
+@pytest.mark.parametrize("shape", [(3, 16, 5, 7), (2, 64, 9, 9), (4, 6, 3, 3), (5, 24),
+                                   (1, 4, 91, 91), (3, 1028, 3, 4), (2, 3, 37, 37)])
 def test_batchnorm_layer(shape):
     from dorknet_amd.layers.batch_norm import BatchNormLayer
     rng = np.random.RandomState(9)

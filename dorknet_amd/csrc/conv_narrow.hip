@@ -484,7 +484,7 @@ static WgrFn wgrad_fn(const Geo& g) {
 static int grid_for(const void* fn, size_t lds, Geo& g) {
   int occ = 0;
   if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&occ, fn, NT, lds) != hipSuccess || occ < 1) occ = 1;
-  const int slots = occ * 256;  // MI355X CUs
+  const int slots = occ * kNumCUs;
   const int grid0 = g.rows < slots ? g.rows : slots;
   g.rpb = cdiv(g.rows, grid0);
   return cdiv(g.rows, g.rpb);

@@ -31,6 +31,8 @@ static inline hipStream_t as_stream(void* s) { return reinterpret_cast<hipStream
 
 static inline int launch_status() { return static_cast<int>(hipGetLastError()); }
 
+constexpr int kNumCUs = 256;  // MI355X: the compute units every grid that fills the chip is sized for
+
 static inline int cdiv(int a, int b) { return (a + b - 1) / b; }
 static inline long long cdivll(long long a, long long b) { return (a + b - 1) / b; }
 

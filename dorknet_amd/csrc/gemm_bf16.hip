@@ -7,25 +7,10 @@ using namespace dk;
 
 // ---------------------------------------------------------------------------------------
 // bf16 storage twins of the pointwise entries (BASELINE config 5).  Activations bf16,
-// weights / statistics / weight gradients fp32; the loaders widen bf16 to fp32 on load and
-// the MFMAs are the exact-fp32 v_mfma_f32_32x32x2_f32 of the fp32 path, so the only
-// numerical difference from fp32 storage is the rounding of each stored activation.
+// weights / statistics / weight gradients fp32; the bodies are the fp32 entries' (gemm_engine.h),
+// taking the storage type from their operands.
 // ---------------------------------------------------------------------------------------
 namespace dk {
-static inline MatDescE<bf16_t> mat_h(const bf16_t* p, int rows, int ld, int ext) {
-  return MatDescE<bf16_t>{p, (uint32_t)((size_t)rows * ld * sizeof(bf16_t)), ld, ext};
-}
-static inline ImgDescE<bf16_t> img_h(const bf16_t* x, int N, int H, int W, int C, int OH, int OW, int R, int S,
-                                     int sa, int dr, int off, int M) {
-  return set_magics(ImgDescE<bf16_t>{x, (uint32_t)((size_t)N * H * W * C * sizeof(bf16_t)), H, W, C, OH, OW, R, S,
-                                     sa, dr, off, off, M});
-}
-static inline ImgDescE<bf16_t, true> img1_h(const bf16_t* x, int N, int H, int W, int C, int OH, int OW, int sa, int M) {
-  return set_magics(ImgDescE<bf16_t, true>{x, (uint32_t)((size_t)N * H * W * C * sizeof(bf16_t)), H, W, C, OH, OW,
-                                           1, 1, sa, 1, 0, 0, M});
-}
-static inline bool al8(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 7) == 0; }
-
 // The path of the three bf16 pointwise operations, each read by its row query and its entry: the
 // weight-stationary deep kernels (pw_deep_bf16.hip: a side of 256+) before the streaming ones
 // (pw_stream_bf16.hip: K, C in {64, 128}; the fused backward K = C = 64) before the tiled engine.
@@ -89,27 +74,9 @@ DK_API int dk_pwconv_fwd_ex_bf16(const bf16_t* x, int N, int H, int W, int C, co
                                                                      bn_gamma, bn_beta, bn_relu, stats, c.plan, st, ft);
     });
   }
-  const ImgDescE<bf16_t, true> a = img1_h(x, N, H, W, C, OH, OW, stride, N * OH * OW);
-  const MatDesc b = mat(w_kc, K, C, K);
-  const int M = a.M;
-  auto run = [&](const auto& da) -> int {
-    using DA = std::decay_t<decltype(da)>;
-    if (stats) {
-      EpStoreStatsT<bf16_t> ep{};
-      ep.out = y, ep.ldo = K, ep.bias = bias, ep.v4 = 1, ep.res = nullptr, ep.part = stats;
-      return igemm_rows<LdImgKC, DA, LdMatKC, MatDesc, EpStoreStatsT<bf16_t>, kRowFwdH, kMfBf16>(da, b, ep, M, K, C, st);
-    }
-    EpStoreT<bf16_t> ep{y, K, bias, 1, nullptr};
-    return igemm_rows<LdImgKC, DA, LdMatKC, MatDesc, EpStoreT<bf16_t>, kRowFwdH, kMfBf16>(da, b, ep, M, K, C, st);
-  };
-  if (bn_mean) {
-    if (!bn_ok(bn_mean, bn_invstd, bn_gamma, bn_beta) || C > 2048) return DK_ERR_ARGS;
-    ImgBnDescE<bf16_t, true> ab;
-    static_cast<ImgDescE<bf16_t, true>&>(ab) = a;
-    ab.bn = BnIn{bn_mean, bn_invstd, bn_gamma, bn_beta, bn_relu};
-    return run(ab);
-  }
-  return run(a);
+  // kRowFwdH: the bf16 pointwise forward's own tile tuning (fp32: kRowPlain), as its row queries above
+  return fwd_rows(img1(x, N, H, W, C, OH, OW, stride, N * OH * OW), w_kc, K, C, bias, y, bn_mean, bn_invstd, bn_gamma,
+                  bn_beta, bn_relu, stats, kRowFwdH, st);
 }
 
 // partial rows of dk_pwconv_dgrad_ex_bf16 (any stride): one per M tile of the tiled engine, the tile
@@ -135,36 +102,9 @@ DK_API int dk_pwconv_dgrad_ex_bf16(const bf16_t* dy, int N, int OH, int OW, int 
   if (!fits((size_t)M * K * 4) || !fits((size_t)M * C * 4 * stride * stride) || (part != nullptr) != (bn_x != nullptr))
     return DK_ERR_ARGS;
   if (part && residual && stride != 1) return DK_ERR_ARGS;  // off-lattice residual terms would need reducing
-  const MatDescE<bf16_t> a = mat_h(dy, M, K, M);
-  const MatDesc b = mat(w_kc, K, C, C);
-  const hipStream_t st = as_stream(stream);
-  if (!part) {
-    if (stride == 1) {
-      EpStoreT<bf16_t> ep{dx, C, nullptr, 1, residual};
-      return igemm_rows<LdMatKC, MatDescE<bf16_t>, LdMatIC, MatDesc, EpStoreT<bf16_t>, kRowPlain, kMfBf16>(a, b, ep, M,
-                                                                                                             C, K, st);
-    }
-    EpWidenT<bf16_t> ep{dx, C, OH, OW, stride, 1, residual};
-    return igemm_rows<LdMatKC, MatDescE<bf16_t>, LdMatIC, MatDesc, EpWidenT<bf16_t>, kRowPlain, kMfBf16>(a, b, ep, M, C,
-                                                                                                           K, st);
-  }
-  if (!bn_ok(bn_mean, bn_invstd, bn_gamma, bn_beta)) return DK_ERR_ARGS;
-  if (stride == 1) {
-    EpStoreBnBwdT<bf16_t> ep{};
-    ep.out = dx, ep.ldo = C, ep.bias = nullptr, ep.v4 = 1, ep.res = residual;
-    ep.part = part;
-    ep.xbn = bn_x;
-    ep.bn = BnIn{bn_mean, bn_invstd, bn_gamma, bn_beta, bn_relu};
-    return igemm_rows<LdMatKC, MatDescE<bf16_t>, LdMatIC, MatDesc, EpStoreBnBwdT<bf16_t>, kRowPlain, kMfBf16>(
-        a, b, ep, M, C, K, st);
-  }
-  EpWidenBnBwdT<bf16_t> ep{};
-  ep.out = dx, ep.ldo = C, ep.OH = OH, ep.OW = OW, ep.st = stride, ep.v4 = 1, ep.res = nullptr;
-  ep.part = part;
-  ep.xbn = bn_x;
-  ep.bn = BnIn{bn_mean, bn_invstd, bn_gamma, bn_beta, bn_relu};
-  return igemm_rows<LdMatKC, MatDescE<bf16_t>, LdMatIC, MatDesc, EpWidenBnBwdT<bf16_t>, kRowPlain, kMfBf16>(
-      a, b, ep, M, C, K, st);
+  if (part && !bn_ok(bn_mean, bn_invstd, bn_gamma, bn_beta)) return DK_ERR_ARGS;
+  return pw_dgrad_tail(dy, M, OH, OW, K, w_kc, C, stride, dx, residual, bn_x,
+                       BnIn{bn_mean, bn_invstd, bn_gamma, bn_beta, bn_relu}, part, as_stream(stream));
 }
 
 // dw[k][c] = sum dy[m][k] * bn(x)[m][c] (+ l2 * w), bf16 activations, fp32 result.
@@ -176,24 +116,12 @@ DK_API int dk_pwconv_wgrad_bnx_bf16(const bf16_t* dy, const bf16_t* x, int N, in
   if (C % 4 || K % 4 || !al8(x) || !al8(dy) || !fits((size_t)N * H * W * C * 4) || !fits((size_t)Kred * K * 4))
     return DK_ERR_ARGS;
   if (ws_bytes < splitk_ws_bytes(K, C, Kred, kMfBf16)) return DK_ERR_WORKSPACE;
-  const MatDescE<bf16_t> a = mat_h(dy, Kred, K, K);
-  const ImgDescE<bf16_t> bi = img_h(x, N, H, W, C, OH, OW, 1, 1, stride, 1, 0, Kred);
-  float* part = static_cast<float*>(ws);
-  const hipStream_t st = as_stream(stream);
-  int splits = 1, rc;
-  if (bn_mean) {
-    if (!bn_ok(bn_mean, bn_invstd, bn_gamma, bn_beta)) return DK_ERR_ARGS;
-    ImgBnDescE<bf16_t> b;
-    static_cast<ImgDescE<bf16_t>&>(b) = bi;
-    b.bn = BnIn{bn_mean, bn_invstd, bn_gamma, bn_beta, bn_relu};
-    rc = igemm_splitk<LdMatIC, MatDescE<bf16_t>, LdImgIC, ImgBnDescE<bf16_t>, kMfBf16>(a, b, part, K, C, Kred, st,
-                                                                                       &splits);
-  } else {
-    rc = igemm_splitk<LdMatIC, MatDescE<bf16_t>, LdImgIC, ImgDescE<bf16_t>, kMfBf16>(a, bi, part, K, C, Kred, st,
-                                                                                     &splits);
-  }
-  if (rc) return rc;
-  return splitk_reduce(part, splits, K, C, dw_kc, w_kc, l2, 0, C, C, 1, 1, st);
+  // (the input BatchNorm is looked at after the workspace: callers see this order)
+  const ImgDescE<bf16_t> b = img(x, N, H, W, C, OH, OW, 1, 1, stride, 1, 0, Kred);
+  if (!bn_mean) return wgrad(dy, b, K, C, w_kc, l2, dw_kc, 0, C, C, 1, 1, ws, ws_bytes, stream);
+  if (!bn_ok(bn_mean, bn_invstd, bn_gamma, bn_beta)) return DK_ERR_ARGS;
+  return wgrad(dy, with_bn(b, bn_mean, bn_invstd, bn_gamma, bn_beta, bn_relu), K, C, w_kc, l2, dw_kc, 0, C, C, 1, 1, ws,
+               ws_bytes, stream);
 }
 
 DK_API int dk_pwconv_dgrad_bnbwd_bf16_stats_rows(int N, int OH, int OW, int K, int C) {
@@ -228,26 +156,10 @@ DK_API int dk_pwconv_dgrad_bnbwd_bf16(const bf16_t* g, const bf16_t* bn_x, int N
           bn_mean, bn_invstd, bn_gamma, bn_beta, bn_relu, part, c.plan, as_stream(stream), ft);
     });
   }
-  MatBwdDescE<bf16_t> a;
-  static_cast<MatDescE<bf16_t>&>(a) = mat_h(g, M, K, M);
-  a.x = bn_x;
-  a.bwd = BnBwdIn{out_mean, out_invstd, out_gamma, out_beta, k12, out_relu, K};
-  a.dy_out = dy_out;
-  const MatDesc b = mat(w_kc, K, C, C);
-  const hipStream_t st = as_stream(stream);
-  if (!part) {
-    EpStoreT<bf16_t> ep{dx, C, nullptr, 1, residual};
-    return igemm_rows<LdMatKC, MatBwdDescE<bf16_t>, LdMatIC, MatDesc, EpStoreT<bf16_t>, kRowBnBwd, kMfBf16>(
-        a, b, ep, M, C, K, st);
-  }
-  if (!bn_ok(bn_mean, bn_invstd, bn_gamma, bn_beta)) return DK_ERR_ARGS;
-  EpStoreBnBwdT<bf16_t> ep{};
-  ep.out = dx, ep.ldo = C, ep.bias = nullptr, ep.v4 = 1, ep.res = residual;
-  ep.part = part;
-  ep.xbn = x;
-  ep.bn = BnIn{bn_mean, bn_invstd, bn_gamma, bn_beta, bn_relu};
-  return igemm_rows<LdMatKC, MatBwdDescE<bf16_t>, LdMatIC, MatDesc, EpStoreBnBwdT<bf16_t>, kRowBnBwd, kMfBf16>(
-      a, b, ep, M, C, K, st);
+  if (part && !bn_ok(bn_mean, bn_invstd, bn_gamma, bn_beta)) return DK_ERR_ARGS;
+  return pw_dgrad_bnbwd_tail(
+      with_bnbwd(mat(g, M, K, M), bn_x, BnBwdIn{out_mean, out_invstd, out_gamma, out_beta, k12, out_relu, K}, dy_out), M, K,
+      w_kc, C, dx, residual, x, BnIn{bn_mean, bn_invstd, bn_gamma, bn_beta, bn_relu}, part, as_stream(stream));
 }
 
 // Fused pointwise backward for bf16 storage (dk_pwconv_bwd_bnbwd_f32's bf16 twin): the dgrad of
@@ -327,27 +239,8 @@ DK_API int dk_conv2d_fwd_ex_bf16(const bf16_t* x, int N, int H, int W, int C, co
     return DK_ERR_ARGS;
   if (N < 1 || R < 1 || S < 1 || stride < 1 || OH < 1 || OW < 1) return DK_ERR_ARGS;
   if (!fits((size_t)N * H * W * C * 4) || !fits((size_t)N * OH * OW * K * 4)) return DK_ERR_ARGS;
-  const hipStream_t st = as_stream(stream);
-  const int M = N * OH * OW, Ktot = R * S * C;
-  const ImgDescE<bf16_t> a = img_h(x, N, H, W, C, OH, OW, R, S, stride, 1, -pad, M);
-  const MatDesc b = mat(w_krsc, K, Ktot, K);
-  auto run = [&](const auto& da) -> int {
-    using DA = std::decay_t<decltype(da)>;
-    if (stats) {
-      EpStoreStatsT<bf16_t> ep{};
-      ep.out = y, ep.ldo = K, ep.bias = bias, ep.v4 = 1, ep.res = nullptr, ep.part = stats;
-      return igemm_rows<LdImgKC, DA, LdMatKC, MatDesc, EpStoreStatsT<bf16_t>, kRowConv, kMfBf16>(da, b, ep, M, K, Ktot,
-                                                                                                 st);
-    }
-    EpStoreT<bf16_t> ep{y, K, bias, 1, nullptr};
-    return igemm_rows<LdImgKC, DA, LdMatKC, MatDesc, EpStoreT<bf16_t>, kRowConv, kMfBf16>(da, b, ep, M, K, Ktot, st);
-  };
-  if (bn_mean) {
-    // (the LDS parameter table holds <= 2048 channels)
-    if (!bn_ok(bn_mean, bn_invstd, bn_gamma, bn_beta) || C > 2048) return DK_ERR_ARGS;
-    return run(with_bn(a, bn_mean, bn_invstd, bn_gamma, bn_beta, bn_relu));
-  }
-  return run(a);
+  return fwd_rows(img(x, N, H, W, C, OH, OW, R, S, stride, 1, -pad, N * OH * OW), w_krsc, K, R * S * C, bias, y,
+                  bn_mean, bn_invstd, bn_gamma, bn_beta, bn_relu, stats, kRowConv, as_stream(stream));
 }
 
 // Stride-1 dgrad (dk_conv2d_dgrad_f32's view): dx[n,h,w,c] = sum_{r,s,k} dy[n, h+pad-r, w+pad-s, k] * w[k][c][r][s]
@@ -355,12 +248,8 @@ DK_API int dk_conv2d_dgrad_bf16(const bf16_t* dy, int N, int OH, int OW, int K, 
                                 int S, int pad, bf16_t* dx, int H, int W, void* stream) {
   if (K < 4 || K % 4 || C < 1 || N < 1 || R < 1 || S < 1 || !al8(dy) || !aligned16(w_crsk) || !dx) return DK_ERR_ARGS;
   if (!fits((size_t)N * OH * OW * K * 4) || !fits((size_t)N * H * W * C * 4)) return DK_ERR_ARGS;
-  const int M = N * H * W, Ktot = R * S * K;
-  const ImgDescE<bf16_t> a = img_h(dy, N, OH, OW, K, H, W, R, S, 1, -1, pad, M);
-  const MatDesc b = mat(w_crsk, C, Ktot, C);
-  EpStoreT<bf16_t> ep{dx, C, nullptr, al4(C) && al8(dx), nullptr};
-  return igemm_rows<LdImgKC, ImgDescE<bf16_t>, LdMatKC, MatDesc, EpStoreT<bf16_t>, kRowConv, kMfBf16>(
-      a, b, ep, M, C, Ktot, as_stream(stream));
+  // kRowConv: the bf16 dense dgrads pick their tile as a convolution (the fp32 twins as kRowPlain)
+  return dgrad_rows(dy, N, OH, OW, K, w_crsk, C, R, S, pad, dx, H, W, kRowConv, as_stream(stream));
 }
 
 // Any-stride dgrad, one implicit GEMM per sub-pixel phase (dk_conv2d_dgrad_phase_f32's geometry and
@@ -371,53 +260,19 @@ DK_API int dk_conv2d_dgrad_phase_bf16(const bf16_t* dy, int N, int OH, int OW, i
   if (Kp % 4 || Kp < K || K < 1 || stride < 1 || stride > 8 || N < 1 || C < 1 || R < 1 || S < 1 || !al8(dy) || !dx ||
       !aligned16(ws))
     return DK_ERR_ARGS;
-  if (ws_bytes < dk_conv2d_dgrad_phase_workspace_bytes(K, C, R, S, stride) || Kp != (K + 3) / 4 * 4)
-    return DK_ERR_WORKSPACE;
-  if (!fits((size_t)N * OH * OW * Kp * 4) || !fits((size_t)N * H * W * C * 4)) return DK_ERR_ARGS;
-  const hipStream_t st = as_stream(stream);
-  float* wsub = static_cast<float*>(ws);
-  int rc = launch_w_phase(w_kcrs, K, C, R, S, stride, pad, Kp, wsub, st);
-  if (rc) return rc;
-  for (int a = 0; a < stride; ++a)
-    for (int b = 0; b < stride; ++b) {
-      const PhaseAxis pa = phase_axis(a, R, stride, pad, H), pb = phase_axis(b, S, stride, pad, W);
-      if (pa.Op == 0 || pb.Op == 0) continue;  // no dx pixels of this phase
-      const int M = N * pa.Op * pb.Op;
-      ImgDescE<bf16_t> d = img_h(dy, N, OH, OW, Kp, pa.Op, pb.Op, pa.Rp, pb.Rp, 1, -1, pa.nb0, M);
-      d.offw = pb.nb0;
-      const int Ktot = pa.Rp * pb.Rp * Kp;
-      const float* wp = wsub + phase_block_offset(a, b, C, R, S, stride, pad, Kp);
-      MatDesc bm = mat(wp, C, Ktot > 0 ? Ktot : 4, C);
-      EpPhaseT<bf16_t> ep{dx, C, pa.Op, pb.Op, H, W, stride, a, b, al4(C) && al8(dx)};
-      rc = igemm_rows<LdImgKC, ImgDescE<bf16_t>, LdMatKC, MatDesc, EpPhaseT<bf16_t>, kRowConv, kMfBf16>(d, bm, ep, M, C,
-                                                                                                       Ktot, st);
-      if (rc) return rc;
-    }
-  return 0;
+  // kRowConv: as dk_conv2d_dgrad_bf16
+  return dgrad_phase_rows(dy, N, OH, OW, Kp, K, w_kcrs, C, R, S, stride, pad, dx, H, W, ws, ws_bytes, kRowConv,
+                          as_stream(stream));
 }
 
 // Weight gradient: dw[k][c][r][s] = sum_{n,oh,ow} dy[n,oh,ow,k] * bn(x)[n, oh*stride + r - pad, ow*stride + s - pad, c]
 // (+ l2 * w), split-K over the pixels into fp32 slabs, then the fixed-order reduce that also drops
-// the channel padding (Cp -> C) -- the fp32 wgrad() helper's steps with bf16 operands.
+// the channel padding (Cp -> C): wgrad() with bf16 operands and their own split rule.
 DK_API size_t dk_conv2d_wgrad_bf16_workspace_bytes(int N, int OH, int OW, int K, int Cp, int R, int S) {
   return splitk_ws_bytes(K, R * S * Cp, N * OH * OW, kMfBf16);
 }
 
 namespace dk {
-template <class D>
-static int wgrad_h(const bf16_t* dy, const D& b, int K, int Ncol, const float* w, float l2, float* dw, int C, int Cp,
-                   int R, int S, void* ws, size_t ws_bytes, void* stream) {
-  const int Kred = b.M;
-  if (!fits((size_t)Kred * K * 4)) return DK_ERR_ARGS;
-  if (ws_bytes < splitk_ws_bytes(K, Ncol, Kred, kMfBf16)) return DK_ERR_WORKSPACE;
-  const MatDescE<bf16_t> a = mat_h(dy, Kred, K, K);
-  int splits = 1;
-  float* part = static_cast<float*>(ws);
-  const hipStream_t st = as_stream(stream);
-  int rc = igemm_splitk<LdMatIC, MatDescE<bf16_t>, LdImgIC, D, kMfBf16>(a, b, part, K, Ncol, Kred, st, &splits);
-  if (rc) return rc;
-  return splitk_reduce(part, splits, K, Ncol, dw, w, l2, 1, C, Cp, R, S, st);
-}
 static inline bool wgrad_h_ok(const bf16_t* dy, const bf16_t* x, int N, int H, int W, int Cp, int C, int K, int R,
                               int S, int stride, const float* dw, const void* ws) {
   return Cp >= 4 && Cp % 4 == 0 && C >= 1 && C <= Cp && K >= 4 && K % 4 == 0 && N >= 1 && R >= 1 && S >= 1 &&
@@ -429,8 +284,8 @@ DK_API int dk_conv2d_wgrad_bf16(const bf16_t* dy, const bf16_t* x, int N, int H,
                                 int S, int stride, int pad, int OH, int OW, const float* w_kcrs, float l2,
                                 float* dw_kcrs, void* ws, size_t ws_bytes, void* stream) {
   if (!wgrad_h_ok(dy, x, N, H, W, Cp, C, K, R, S, stride, dw_kcrs, ws)) return DK_ERR_ARGS;
-  return wgrad_h(dy, img_h(x, N, H, W, Cp, OH, OW, R, S, stride, 1, -pad, N * OH * OW), K, R * S * Cp, w_kcrs, l2,
-                 dw_kcrs, C, Cp, R, S, ws, ws_bytes, stream);
+  return wgrad(dy, img(x, N, H, W, Cp, OH, OW, R, S, stride, 1, -pad, N * OH * OW), K, R * S * Cp, w_kcrs, l2,
+               dw_kcrs, 1, C, Cp, R, S, ws, ws_bytes, stream);
 }
 
 DK_API int dk_conv2d_wgrad_bnx_bf16(const bf16_t* dy, const bf16_t* x, int N, int H, int W, int Cp, int C, int K,
@@ -440,8 +295,8 @@ DK_API int dk_conv2d_wgrad_bnx_bf16(const bf16_t* dy, const bf16_t* x, int N, in
                                     void* stream) {
   if (!wgrad_h_ok(dy, x, N, H, W, Cp, C, K, R, S, stride, dw_kcrs, ws)) return DK_ERR_ARGS;
   if (!bn_ok(bn_mean, bn_invstd, bn_gamma, bn_beta)) return DK_ERR_ARGS;
-  return wgrad_h(dy,
-                 with_bn(img_h(x, N, H, W, Cp, OH, OW, R, S, stride, 1, -pad, N * OH * OW), bn_mean, bn_invstd,
-                         bn_gamma, bn_beta, bn_relu),
-                 K, R * S * Cp, w_kcrs, l2, dw_kcrs, C, Cp, R, S, ws, ws_bytes, stream);
+  return wgrad(dy,
+               with_bn(img(x, N, H, W, Cp, OH, OW, R, S, stride, 1, -pad, N * OH * OW), bn_mean, bn_invstd, bn_gamma,
+                       bn_beta, bn_relu),
+               K, R * S * Cp, w_kcrs, l2, dw_kcrs, 1, C, Cp, R, S, ws, ws_bytes, stream);
 }

@@ -92,20 +92,17 @@ DK_API int dk_conv_weight_crsk_f32(const float* w_kcrs, int K, int C, int R, int
 
 DK_API int dk_conv2d_fwd_f32(const float* x, int N, int H, int W, int C, const float* w_krsc, int K, int R, int S,
                              int stride, int pad, const float* bias, float* y, int OH, int OW, void* stream) {
-  if (C % 4 || !aligned16(x) || !aligned16(w_krsc) || !fits((size_t)N * H * W * C * 4)) return DK_ERR_ARGS;
-  return conv_fwd(img(x, N, H, W, C, OH, OW, R, S, stride, 1, -pad, N * OH * OW), w_krsc, K, R * S * C, bias, y,
-                  stream);
+  return dk_conv2d_fwd_ex_f32(x, N, H, W, C, w_krsc, K, R, S, stride, pad, bias, y, OH, OW, nullptr, nullptr, nullptr,
+                              nullptr, 0, nullptr, stream);
 }
 
 DK_API int dk_conv2d_fwd_bnx_f32(const float* x, int N, int H, int W, int C, const float* w_krsc, int K, int R, int S,
                                  int stride, int pad, const float* bias, float* y, int OH, int OW,
                                  const float* bn_mean, const float* bn_invstd, const float* bn_gamma,
                                  const float* bn_beta, int bn_relu, void* stream) {
-  if (C % 4 || !aligned16(x) || !aligned16(w_krsc) || !fits((size_t)N * H * W * C * 4)) return DK_ERR_ARGS;
-  if (!bn_ok(bn_mean, bn_invstd, bn_gamma, bn_beta)) return DK_ERR_ARGS;
-  return conv_fwd(with_bn(img(x, N, H, W, C, OH, OW, R, S, stride, 1, -pad, N * OH * OW), bn_mean, bn_invstd,
-                          bn_gamma, bn_beta, bn_relu),
-                  w_krsc, K, R * S * C, bias, y, stream);
+  if (!bn_mean) return DK_ERR_ARGS;  // (to the _ex entry NULL means no input BatchNorm)
+  return dk_conv2d_fwd_ex_f32(x, N, H, W, C, w_krsc, K, R, S, stride, pad, bias, y, OH, OW, bn_mean, bn_invstd,
+                              bn_gamma, bn_beta, bn_relu, nullptr, stream);
 }
 
 DK_API int dk_conv2d_fwd_stats_rows(int N, int OH, int OW, int K, int C, int R, int S) {
@@ -119,19 +116,16 @@ DK_API int dk_conv2d_fwd_ex_f32(const float* x, int N, int H, int W, int C, cons
                                 const float* bn_mean, const float* bn_invstd, const float* bn_gamma,
                                 const float* bn_beta, int bn_relu, double* stats, void* stream) {
   if (C % 4 || !aligned16(x) || !aligned16(w_krsc) || !fits((size_t)N * H * W * C * 4)) return DK_ERR_ARGS;
-  return conv_fwd_ex(img(x, N, H, W, C, OH, OW, R, S, stride, 1, -pad, N * OH * OW), w_krsc, K, R * S * C, bias, y,
-                     bn_mean, bn_invstd, bn_gamma, bn_beta, bn_relu, stats, stream);
+  return fwd_rows(img(x, N, H, W, C, OH, OW, R, S, stride, 1, -pad, N * OH * OW), w_krsc, K, R * S * C, bias, y,
+                  bn_mean, bn_invstd, bn_gamma, bn_beta, bn_relu, stats, kRowConv, as_stream(stream));
 }
 
-// Stride-1 dgrad as an implicit GEMM: dx[n,h,w,c] = sum_{r,s,k} dy[n, h+pad-r, w+pad-s, k] * w[k][c][r][s]
+// Stride-1 dgrad (dgrad_rows)
 DK_API int dk_conv2d_dgrad_f32(const float* dy, int N, int OH, int OW, int K, const float* w_crsk, int C, int R,
                                int S, int pad, float* dx, int H, int W, void* stream) {
   if (K % 4 || !aligned16(dy) || !aligned16(w_crsk) || !fits((size_t)N * OH * OW * K * 4)) return DK_ERR_ARGS;
-  ImgDesc a = img(dy, N, OH, OW, K, H, W, R, S, 1, -1, pad, N * H * W);
-  const int Ktot = R * S * K;
-  MatDesc b = mat(w_crsk, C, Ktot, C);
-  EpStore ep = ep_store(dx, C, nullptr);
-  return igemm_rows<LdImgKC, ImgDesc, LdMatKC, MatDesc, EpStore>(a, b, ep, N * H * W, C, Ktot, as_stream(stream));
+  // kRowPlain: the fp32 dense dgrads pick their tile as a plain GEMM (the bf16 twins as kRowConv)
+  return dgrad_rows(dy, N, OH, OW, K, w_crsk, C, R, S, pad, dx, H, W, kRowPlain, as_stream(stream));
 }
 
 DK_API size_t dk_conv2d_dgrad_phase_workspace_bytes(int K, int C, int R, int S, int stride) {
@@ -141,37 +135,17 @@ DK_API size_t dk_conv2d_dgrad_phase_workspace_bytes(int K, int C, int R, int S, 
 }
 
 // Input gradient of any-stride convolution as one implicit GEMM per sub-pixel phase (replaces
-// cp.dot(dy, W_flat) + row2im, convolution.py:101-117 / :205-222: no column matrix, no atomics):
-// phase (a, b) is a stride-1 correlation of dy with its sub-filter, written to the dx pixels
-// (st*i + a, st*j + b).  dy has Kp = K rounded up to 4 channels (zero-padded by the caller when
-// K % 4 != 0); phases with no taps (R or S < stride) write zeros.
+// cp.dot(dy, W_flat) + row2im, convolution.py:101-117 / :205-222: no column matrix, no atomics;
+// dgrad_phase_rows).  dy has Kp = K rounded up to 4 channels (zero-padded by the caller when
+// K % 4 != 0).
 DK_API int dk_conv2d_dgrad_phase_f32(const float* dy, int N, int OH, int OW, int Kp, int K, const float* w_kcrs,
                                      int C, int R, int S, int stride, int pad, float* dx, int H, int W, void* ws,
                                      size_t ws_bytes, void* stream) {
   if (Kp % 4 || Kp < K || stride < 1 || stride > 8 || N < 1 || C < 1 || !aligned16(dy) || !aligned16(ws))
     return DK_ERR_ARGS;
-  if (ws_bytes < dk_conv2d_dgrad_phase_workspace_bytes(K, C, R, S, stride) || Kp != (K + 3) / 4 * 4)
-    return DK_ERR_WORKSPACE;
-  if (!fits((size_t)N * OH * OW * Kp * 4) || !fits((size_t)N * H * W * C * 4)) return DK_ERR_ARGS;
-  const hipStream_t st = as_stream(stream);
-  float* wsub = static_cast<float*>(ws);
-  int rc = launch_w_phase(w_kcrs, K, C, R, S, stride, pad, Kp, wsub, st);
-  if (rc) return rc;
-  for (int a = 0; a < stride; ++a)
-    for (int b = 0; b < stride; ++b) {
-      const PhaseAxis pa = phase_axis(a, R, stride, pad, H), pb = phase_axis(b, S, stride, pad, W);
-      if (pa.Op == 0 || pb.Op == 0) continue;  // no dx pixels of this phase
-      const int M = N * pa.Op * pb.Op;
-      ImgDesc d = img(dy, N, OH, OW, Kp, pa.Op, pb.Op, pa.Rp, pb.Rp, 1, -1, pa.nb0, M);
-      d.offw = pb.nb0;
-      const int Ktot = pa.Rp * pb.Rp * Kp;
-      const float* wp = wsub + phase_block_offset(a, b, C, R, S, stride, pad, Kp);
-      MatDesc bm = mat(wp, C, Ktot > 0 ? Ktot : 4, C);
-      EpPhase ep{dx, C, pa.Op, pb.Op, H, W, stride, a, b, al4(C) && aligned16(dx)};
-      rc = igemm_rows<LdImgKC, ImgDesc, LdMatKC, MatDesc, EpPhase>(d, bm, ep, M, C, Ktot, st);
-      if (rc) return rc;
-    }
-  return 0;
+  // kRowPlain: as dk_conv2d_dgrad_f32
+  return dgrad_phase_rows(dy, N, OH, OW, Kp, K, w_kcrs, C, R, S, stride, pad, dx, H, W, ws, ws_bytes, kRowPlain,
+                          as_stream(stream));
 }
 
 DK_API size_t dk_conv2d_wgrad_workspace_bytes(int N, int OH, int OW, int K, int Cp, int R, int S) {
@@ -219,5 +193,3 @@ DK_API int dk_conv2d_wgrad_bnx_f32(const float* dy, const float* x, int N, int H
                        bn_beta, bn_relu),
                K, R * S * Cp, w_kcrs, l2, dw_kcrs, 1, C, Cp, R, S, ws, ws_bytes, stream);
 }
-
-// Pointwise (1x1) forward with optional stride-s subsampling (pointwise_convolution.py:46-55):

@@ -11,8 +11,9 @@ DK_API int dk_dense_fwd_f32(const float* x, int B, int IN, const float* w_io, in
   EpStore ep = ep_store(y, OUT, bias);
   const hipStream_t st = as_stream(stream);
   const bool va = vec_ok(a, IN, 4), vb = vec_ok(b, 4, OUT);
-  if (va && vb) return igemm_rows<LdMatKC, MatDesc, LdMatIC, MatDesc, EpStore>(a, b, ep, B, OUT, IN, st);
-  return igemm_rows<LdMatKC1, MatDesc, LdMatIC1, MatDesc, EpStore>(a, b, ep, B, OUT, IN, st);
+  // (the scalar loaders: operands that rule out 16-byte loads)
+  if (va && vb) return igemm_rows<LdMatKC, LdMatIC>(a, b, ep, B, OUT, IN, kRowPlain, st);
+  return igemm_rows<LdMatKC1, LdMatIC1>(a, b, ep, B, OUT, IN, kRowPlain, st);
 }
 
 // dx[b][i] = sum_o dy[b][o] * w[i][o]   (dense_layer.py:67)
@@ -22,8 +23,8 @@ DK_API int dk_dense_dgrad_f32(const float* dy, int B, int OUT, const float* w_io
   EpStore ep = ep_store(dx, IN, nullptr);
   const hipStream_t st = as_stream(stream);
   if (vec_ok(a, OUT, 4) && vec_ok(b, OUT, 4))
-    return igemm_rows<LdMatKC, MatDesc, LdMatKC, MatDesc, EpStore>(a, b, ep, B, IN, OUT, st);
-  return igemm_rows<LdMatKC1, MatDesc, LdMatKC1, MatDesc, EpStore>(a, b, ep, B, IN, OUT, st);
+    return igemm_rows<LdMatKC, LdMatKC>(a, b, ep, B, IN, OUT, kRowPlain, st);
+  return igemm_rows<LdMatKC1, LdMatKC1>(a, b, ep, B, IN, OUT, kRowPlain, st);
 }
 
 DK_API size_t dk_dense_wgrad_workspace_bytes(int B, int IN, int OUT) { return splitk_ws_bytes(IN, OUT, B); }
@@ -38,9 +39,9 @@ DK_API int dk_dense_wgrad_f32(const float* x, const float* dy, int B, int IN, in
   const hipStream_t st = as_stream(stream);
   int rc;
   if (vec_ok(a, 4, IN) && vec_ok(b, 4, OUT))
-    rc = igemm_splitk<LdMatIC, MatDesc, LdMatIC, MatDesc>(a, b, static_cast<float*>(ws), IN, OUT, B, st, &splits);
+    rc = igemm_splitk<LdMatIC, LdMatIC>(a, b, static_cast<float*>(ws), IN, OUT, B, st, &splits);
   else
-    rc = igemm_splitk<LdMatIC1, MatDesc, LdMatIC1, MatDesc>(a, b, static_cast<float*>(ws), IN, OUT, B, st, &splits);
+    rc = igemm_splitk<LdMatIC1, LdMatIC1>(a, b, static_cast<float*>(ws), IN, OUT, B, st, &splits);
   if (rc) return rc;
   return splitk_reduce(static_cast<float*>(ws), splits, IN, OUT, dw_io, w_io, l2, 0, OUT, OUT, 1, 1, st);
 }

@@ -1045,19 +1045,12 @@ __global__ __launch_bounds__(64 * WM * WN) void igemm_f32(DA da, DB db, EP ep, i
 }
 
 static inline int aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
+static inline bool al8(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 7) == 0; }
 
 // Buffer resources address < 2 GiB (32-bit offsets with kOOB as the out-of-range marker).
 static inline bool fits(size_t bytes) { return bytes < ((size_t)1 << 31); }
 
 static inline int al4(int v) { return (v & 3) == 0; }
-static inline EpStore ep_store(float* out, int ldo, const float* bias, const float* res = nullptr) {
-  return EpStore{out, ldo, bias, al4(ldo) && aligned16(out) && (!bias || aligned16(bias)) && (!res || aligned16(res)),
-                 res};
-}
-static inline EpWiden ep_widen(float* out, int ldo, int OH, int OW, int st, const float* res = nullptr) {
-  return EpWiden{out, ldo, OH, OW, st, al4(ldo) && aligned16(out) && (!res || aligned16(res)), res};
-}
-
 
 // ----------------------------------------------------------------------------
 // Host-side launch helpers and tile selection
@@ -1110,7 +1103,6 @@ static const int kNumSplitCfg = sizeof(kSplitCfg) / sizeof(kSplitCfg[0]);
 // dk_debug_set_gemm_config(2, 0/1)).  A persistent tile loop for the row problems was measured
 // and dropped (scripts/ab_step.py: 11.77 ms/step with one block per tile, 11.89 / 11.98 with
 // 1 / 2 resident waves of persistent blocks, and the loop slowed the one-tile case too).
-constexpr int kNumCUs = 256;  // MI355X
 
 // Epilogues with an `nt` member take the nontemporal-store knob (nt_stores()).
 template <class E>
@@ -1190,21 +1182,19 @@ static int launch_igemm(const DA& da, const DB& db, const EP& ep, int M, int N, 
   const int kps = KT > 0 ? cdiv(KT, splits) : 1;
   splits = KT > 0 ? cdiv(KT, kps) : 1;
   if (splits_used) *splits_used = splits;
+  EP e = ep;
+  set_nt(e, 0);
   if constexpr (EP::kColStats) {
     // an armed in-launch fold of the column statistics (fold_tail.h): rows = M tiles, one
     // channel slice per N tile
-    EP e = ep;
-    set_nt(e, 0);
     if (!e.part || splits != 1 || !fold_take(e.part, cdiv(M, BM), N, cdiv(N, BN), &e.ft)) e.ft.part = nullptr;
-    hipLaunchKernelGGL((igemm_f32<BM, BN, BK, WM, WN, A, DA, B, DB, EP, MF>), dim3(tiles, splits), dim3(NT), dyn, st, da,
-                       db, e, M, N, Ktot, kps);
-    return fold_status(launch_status(), e.ft);
   }
-  EP e = ep;
-  set_nt(e, 0);
   hipLaunchKernelGGL((igemm_f32<BM, BN, BK, WM, WN, A, DA, B, DB, EP, MF>), dim3(tiles, splits), dim3(NT), dyn, st, da,
                      db, e, M, N, Ktot, kps);
-  return launch_status();
+  if constexpr (EP::kColStats)
+    return fold_status(launch_status(), e.ft);
+  else
+    return launch_status();
 }
 
 // Row-problem kinds with their own tile choice: plain loaders, and the BN-backward-on-load A
@@ -1247,11 +1237,16 @@ static inline int row_config(int M, int N, int K, int kind = kRowPlain, int mf =
   return K <= 128 ? 6 : 8;
 }
 
-// Output-stationary problems (fwd / dgrad).
-template <template <int, int, int> class LA, class DA, template <int, int, int> class LB, class DB, class EP,
-          int KIND = kRowPlain, int MF = kMfF32>
-static int igemm_rows(const DA& da, const DB& db, const EP& ep, int M, int N, int Ktot, hipStream_t st) {
-  switch (row_config(M, N, Ktot, KIND, MF)) {
+// The MFMA mode of an element type: bf16 storage runs the bf16 MFMAs, fp32 the exact-fp32 ones.
+template <class E>
+constexpr int kMfOf = std::is_same<E, bf16_t>::value ? kMfBf16 : kMfF32;
+
+// Output-stationary problems (fwd / dgrad).  The loaders are named; descriptors and epilogue are
+// deduced, the MFMA mode follows the A operand's element type, `kind` only picks the tile.
+template <template <int, int, int> class LA, template <int, int, int> class LB, class DA, class DB, class EP>
+static int igemm_rows(const DA& da, const DB& db, const EP& ep, int M, int N, int Ktot, int kind, hipStream_t st) {
+  constexpr int MF = kMfOf<typename DA::Elem>;
+  switch (row_config(M, N, Ktot, kind, MF)) {
 #define DK_CASE(id, bm, bn, bk, wm, wn) \
   case id:                              \
     return launch_igemm<bm, bn, bk, wm, wn, LA, DA, LB, DB, EP, MF>(da, db, ep, M, N, Ktot, 1, st);
@@ -1296,9 +1291,10 @@ static inline int wgrad_splits(int M, int N, int Kred, const TileCfg& c) {
   return cdiv(KT, kps);
 }
 
-template <template <int, int, int> class LA, class DA, template <int, int, int> class LB, class DB, int MF = kMfF32>
+template <template <int, int, int> class LA, template <int, int, int> class LB, class DA, class DB>
 static int igemm_splitk(const DA& da, const DB& db, float* ws, int M, int N, int Kred, hipStream_t st,
                         int* splits_out) {
+  constexpr int MF = kMfOf<typename DA::Elem>;
   const int id = splitk_config(M, N, Kred, MF);
   if (id < 0 || id >= kNumSplitCfg) return DK_ERR_ARGS;
   const int splits = wgrad_splits(M, N, Kred, kSplitCfg[id]);  // the workspace's upper bound
@@ -1355,10 +1351,17 @@ int launch_w_phase(const float* w_kcrs, int K, int C, int R, int S, int stride, 
                    hipStream_t st);
 
 
+// ----------------------------------------------------------------------------
+// The host layer: small pure builders of operands and epilogues, and one
+// body per route.  Builders and bodies take the storage type (float or bf16_t) from their
+// pointers; an exported entry keeps its own argument checks, builds its operands and calls a body.
+// ----------------------------------------------------------------------------
+
 // rows x ld matrix; ext = extent of the non-reduction index (rows for a K-contiguous
 // operand, valid columns for a row-contiguous one).
-static inline MatDesc mat(const float* p, int rows, int ld, int ext) {
-  return MatDesc{p, (uint32_t)((size_t)rows * ld * sizeof(float)), ld, ext};
+template <class E>
+static inline MatDescE<E> mat(const E* p, int rows, int ld, int ext) {
+  return MatDescE<E>{p, (uint32_t)((size_t)rows * ld * sizeof(E)), ld, ext};
 }
 static inline bool vec_ok(const MatDesc& d, int kext, int iext) {
   return d.ld % 4 == 0 && kext % 4 == 0 && iext % 4 == 0 && aligned16(d.p);
@@ -1378,18 +1381,20 @@ static inline Dsc set_magics(Dsc d) {
   d.mOH = magic(d.OH, d.M);
   return d;
 }
-static inline ImgDesc img(const float* x, int N, int H, int W, int C, int OH, int OW, int R, int S, int sa, int dr,
-                          int off, int M) {
+template <class E>
+static inline ImgDescE<E> img(const E* x, int N, int H, int W, int C, int OH, int OW, int R, int S, int sa, int dr,
+                              int off, int M) {
   return set_magics(
-      ImgDesc{x, (uint32_t)((size_t)N * H * W * C * sizeof(float)), H, W, C, OH, OW, R, S, sa, dr, off, off, M});
+      ImgDescE<E>{x, (uint32_t)((size_t)N * H * W * C * sizeof(E)), H, W, C, OH, OW, R, S, sa, dr, off, off, M, 0, 0, 0, 0});
 }
 // A pointwise (1x1, stride sa) view: k = channel.
-static inline ImgDescE<float, true> img1(const float* x, int N, int H, int W, int C, int OH, int OW, int sa, int M) {
-  return set_magics(ImgDescE<float, true>{x, (uint32_t)((size_t)N * H * W * C * sizeof(float)), H, W, C, OH, OW, 1,
-                                          1, sa, 1, 0, 0, M});
+template <class E>
+static inline ImgDescE<E, true> img1(const E* x, int N, int H, int W, int C, int OH, int OW, int sa, int M) {
+  return set_magics(ImgDescE<E, true>{x, (uint32_t)((size_t)N * H * W * C * sizeof(E)), H, W, C, OH, OW, 1, 1, sa, 1,
+                                      0, 0, M, 0, 0, 0, 0});
 }
 
-// y[n,oh,ow,k] = sum_{r,s,c} x[n, oh*stride + r - pad, ow*stride + s - pad, c] * w[k][r][s][c] (+ bias[k])
+// The same view of bn(x) (+ReLU) / the matrix with the following BatchNorm's backward applied on load.
 template <class E, bool K1>
 static inline ImgBnDescE<E, K1> with_bn(const ImgDescE<E, K1>& d, const float* mean, const float* invstd,
                                         const float* gamma, const float* beta, int relu) {
@@ -1398,64 +1403,184 @@ static inline ImgBnDescE<E, K1> with_bn(const ImgDescE<E, K1>& d, const float* m
   o.bn = BnIn{mean, invstd, gamma, beta, relu};
   return o;
 }
+template <class E>
+static inline MatBwdDescE<E> with_bnbwd(const MatDescE<E>& d, const E* bn_x, const BnBwdIn& bw, E* dy_out) {
+  MatBwdDescE<E> o;
+  static_cast<MatDescE<E>&>(o) = d;
+  o.x = bn_x;
+  o.bwd = bw;
+  o.dy_out = dy_out;
+  return o;
+}
 static inline bool bn_ok(const float* mean, const float* invstd, const float* gamma, const float* beta) {
   return mean && invstd && gamma && beta && aligned16(mean) && aligned16(invstd) && aligned16(gamma) &&
          aligned16(beta);
 }
 
-template <class D>
-static int conv_fwd(const D& a, const float* w_krsc, int K, int Ktot, const float* bias, float* y, void* stream,
-                    double* stats = nullptr) {
-  if constexpr (D::kBnIn) {
-    if (a.C > 2048) return DK_ERR_ARGS;  // the LDS parameter table holds <= 2048 channels (32 KB)
-  }
-  MatDesc b = mat(w_krsc, K, Ktot, K);
-  constexpr int kind = D::k1x1 ? kRowPlain : kRowConv;
-  if (stats) {
-    EpStoreStats ep;
-    static_cast<EpStore&>(ep) = ep_store(y, K, bias);
-    ep.part = stats;
-    return igemm_rows<LdImgKC, D, LdMatKC, MatDesc, EpStoreStats, kind>(a, b, ep, a.M, K, Ktot, as_stream(stream));
-  }
-  EpStore ep = ep_store(y, K, bias);
-  return igemm_rows<LdImgKC, D, LdMatKC, MatDesc, EpStore, kind>(a, b, ep, a.M, K, Ktot, as_stream(stream));
+// Epilogues.  v4 = every tensor the epilogue touches allows access in groups of 4 elements: 16 bytes
+// of fp32 (bias, BN vectors, fp32 activations), 8 bytes of bf16 activations.
+template <class O>
+static inline bool vec4_ok(const O* p) {
+  return (reinterpret_cast<uintptr_t>(p) & (4 * sizeof(O) - 1)) == 0;
+}
+template <class O>
+static inline EpStoreT<O> ep_store(O* out, int ldo, const float* bias, const O* res = nullptr) {
+  return EpStoreT<O>{out, ldo, bias, al4(ldo) && vec4_ok(out) && (!bias || aligned16(bias)) && (!res || vec4_ok(res)),
+                     res};
+}
+template <class O>
+static inline EpWidenT<O> ep_widen(O* out, int ldo, int OH, int OW, int st, const O* res = nullptr) {
+  return EpWidenT<O>{out, ldo, OH, OW, st, al4(ldo) && vec4_ok(out) && (!res || vec4_ok(res)), res};
+}
+// + the output's column statistics (EpStoreStatsT)
+template <class O>
+static inline EpStoreStatsT<O> ep_stats(const EpStoreT<O>& e, double* part) {
+  EpStoreStatsT<O> o{};
+  static_cast<EpStoreT<O>&>(o) = e;
+  o.part = part;
+  return o;
+}
+// + the BN-backward partials of the BatchNorm whose output the layer consumed (EPB = EpStoreBnBwdT,
+// EpWidenBnBwdT or EpLatticeBnBwd over its base e): xbn = that BN's raw input; v4 also needs xbn and
+// the BN vectors loadable in groups of 4
+template <class EPB, class EP, class O>
+static inline EPB ep_bnbwd(const EP& e, double* part, const O* xbn, const BnIn& bn) {
+  EPB o{};
+  static_cast<EP&>(o) = e;
+  o.v4 = o.v4 && vec4_ok(xbn) && bn_ok(bn.mean, bn.invstd, bn.gamma, bn.beta);
+  o.part = part;
+  o.xbn = xbn;
+  o.bn = bn;
+  return o;
 }
 
-// Rows of BatchNorm partial statistics a *_fwd_ex_f32 call writes (one per output tile row).
+// Rows of BatchNorm partial statistics a launch of that kind writes (one per output tile row).
 static inline int stats_rows(int M, int N, int Ktot, int kind = kRowPlain, int mf = kMfF32) {
   return cdiv(M, kRowCfg[row_config(M, N, Ktot, kind, mf)].BM);
 }
 
-// Forward with an optional input BatchNorm (bn_mean != NULL, see *_bnx_*) and optional output
-// statistics (stats != NULL: stats_rows x 2 x K doubles).
-template <class D0>
-static int conv_fwd_ex(const D0& base, const float* w, int K, int Ktot, const float* bias, float* y,
-                       const float* bn_mean, const float* bn_invstd, const float* bn_gamma, const float* bn_beta,
-                       int bn_relu, double* stats, void* stream) {
-  if (bn_mean) {
-    if (!bn_ok(bn_mean, bn_invstd, bn_gamma, bn_beta)) return DK_ERR_ARGS;
-    return conv_fwd(with_bn(base, bn_mean, bn_invstd, bn_gamma, bn_beta, bn_relu), w, K, Ktot, bias, y, stream, stats);
-  }
-  return conv_fwd(base, w, K, Ktot, bias, y, stream, stats);
+// Forward tail: y[m][k] = sum a(m, .) * w[k][.] (+ bias), a = an image view with an optional input
+// BatchNorm on load (bn_mean != NULL) and optional output statistics (stats != NULL: stats_rows x 2 x K
+// doubles).  kind: kRowConv for R x S images, kRowPlain for fp32 1x1 views, kRowFwdH for bf16 ones.
+template <class D, class O>
+static int fwd_rows(const D& base, const float* w, int K, int Ktot, const float* bias, O* y, const float* bn_mean,
+                    const float* bn_invstd, const float* bn_gamma, const float* bn_beta, int bn_relu, double* stats,
+                    int kind, hipStream_t st) {
+  const MatDesc b = mat(w, K, Ktot, K);
+  auto run = [&](const auto& a) -> int {
+    const EpStoreT<O> ep = ep_store(y, K, bias);
+    if (stats) return igemm_rows<LdImgKC, LdMatKC>(a, b, ep_stats(ep, stats), a.M, K, Ktot, kind, st);
+    return igemm_rows<LdImgKC, LdMatKC>(a, b, ep, a.M, K, Ktot, kind, st);
+  };
+  if (!bn_mean) return run(base);
+  // (the LDS parameter table holds <= 2048 channels, 32 KB)
+  if (!bn_ok(bn_mean, bn_invstd, bn_gamma, bn_beta) || base.C > 2048) return DK_ERR_ARGS;
+  return run(with_bn(base, bn_mean, bn_invstd, bn_gamma, bn_beta, bn_relu));
 }
 
-// dw[k][c][r][s] = sum_{n,oh,ow} dy[n,oh,ow,k] * x[n, oh*stride + r - pad, ow*stride + s - pad, c]  (+ l2 * w)
-// Weight gradient through the split-K engine: part = dy^T . im2col(x) then the fixed-order
-// reduce (+ l2 * w) into the KCRS (mode 1) or [K][C] (mode 0) layout.
-template <class D>
-static int wgrad(const float* dy, const D& b, int K, int Ncol, const float* w, float l2, float* dw, int mode, int C,
-                 int Cp, int R, int S, void* ws, size_t ws_bytes, void* stream) {
-  const int Kred = b.M;
-  if (!fits((size_t)Kred * K * 4)) return DK_ERR_ARGS;
-  if (ws_bytes < splitk_ws_bytes(K, Ncol, Kred)) return DK_ERR_WORKSPACE;
-  MatDesc a = mat(dy, Kred, K, K);
+// Stride-1 dgrad as an implicit GEMM: dx[n,h,w,c] = sum_{r,s,k} dy[n, h+pad-r, w+pad-s, k] * w[k][c][r][s].
+// kind: kRowPlain for fp32, kRowConv for bf16 -- each dtype's own tile tuning, not to be unified.
+template <class E>
+static int dgrad_rows(const E* dy, int N, int OH, int OW, int K, const float* w_crsk, int C, int R, int S, int pad,
+                      E* dx, int H, int W, int kind, hipStream_t st) {
+  const int M = N * H * W, Ktot = R * S * K;
+  return igemm_rows<LdImgKC, LdMatKC>(img(dy, N, OH, OW, K, H, W, R, S, 1, -1, pad, M), mat(w_crsk, C, Ktot, C),
+                                      ep_store(dx, C, nullptr), M, C, Ktot, kind, st);
+}
+
+// Any-stride dgrad, one implicit GEMM per sub-pixel phase: phase (a, b) is a stride-1 correlation of
+// dy with its sub-filter (w_phase_kernel, fp32, into ws), written to the dx pixels (st*i + a, st*j + b);
+// phases with no taps (R or S < stride) write zeros.  kind as dgrad_rows.
+template <class E>
+static int dgrad_phase_rows(const E* dy, int N, int OH, int OW, int Kp, int K, const float* w_kcrs, int C, int R,
+                            int S, int stride, int pad, E* dx, int H, int W, void* ws, size_t ws_bytes, int kind,
+                            hipStream_t st) {
+  // the workspace (and the padded channel count) before the 2 GiB limits: callers see this order
+  if (ws_bytes < dk_conv2d_dgrad_phase_workspace_bytes(K, C, R, S, stride) || Kp != (K + 3) / 4 * 4)
+    return DK_ERR_WORKSPACE;
+  if (!fits((size_t)N * OH * OW * Kp * 4) || !fits((size_t)N * H * W * C * 4)) return DK_ERR_ARGS;
+  float* wsub = static_cast<float*>(ws);
+  int rc = launch_w_phase(w_kcrs, K, C, R, S, stride, pad, Kp, wsub, st);
+  if (rc) return rc;
+  for (int a = 0; a < stride; ++a)
+    for (int b = 0; b < stride; ++b) {
+      const PhaseAxis pa = phase_axis(a, R, stride, pad, H), pb = phase_axis(b, S, stride, pad, W);
+      if (pa.Op == 0 || pb.Op == 0) continue;  // no dx pixels of this phase
+      const int M = N * pa.Op * pb.Op;
+      ImgDescE<E> d = img(dy, N, OH, OW, Kp, pa.Op, pb.Op, pa.Rp, pb.Rp, 1, -1, pa.nb0, M);
+      d.offw = pb.nb0;
+      const int Ktot = pa.Rp * pb.Rp * Kp;
+      const float* wp = wsub + phase_block_offset(a, b, C, R, S, stride, pad, Kp);
+      const EpPhaseT<E> ep{dx, C, pa.Op, pb.Op, H, W, stride, a, b, al4(C) && vec4_ok(dx)};
+      rc = igemm_rows<LdImgKC, LdMatKC>(d, mat(wp, C, Ktot > 0 ? Ktot : 4, C), ep, M, C, Ktot, kind, st);
+      if (rc) return rc;
+    }
+  return 0;
+}
+
+// Pointwise dgrad rows dx = dy . W: the 16-byte loaders, or for fp32 operands that rule them out the
+// scalar ones (the bf16 entries refuse such operands, and have no scalar form)
+template <class E, class EP>
+static int pw_dgrad_rows(const MatDescE<E>& a, const MatDesc& b, const EP& ep, int M, int C, int K, hipStream_t st) {
+  if constexpr (std::is_same<E, float>::value) {
+    if (!(vec_ok(a, K, 4) && vec_ok(b, 4, C))) return igemm_rows<LdMatKC1, LdMatIC1>(a, b, ep, M, C, K, kRowPlain, st);
+  }
+  return igemm_rows<LdMatKC, LdMatIC>(a, b, ep, M, C, K, kRowPlain, st);
+}
+
+// The tiled tail of dk_pwconv_dgrad[_ex]_*: dx = dy . W (+ residual), stored (stride 1) or widened to
+// the (OH*stride) x (OW*stride) grid, and with part the BN-backward partials of bn over (dx, bn_x).
+template <class E>
+static int pw_dgrad_tail(const E* dy, int M, int OH, int OW, int K, const float* w_kc, int C, int stride, E* dx,
+                         const E* residual, const E* bn_x, const BnIn& bn, double* part, hipStream_t st) {
+  const MatDescE<E> a = mat(dy, M, K, M);
+  const MatDesc b = mat(w_kc, K, C, C);
+  if (stride == 1) {
+    const EpStoreT<E> ep = ep_store(dx, C, nullptr, residual);
+    if (!part) return pw_dgrad_rows(a, b, ep, M, C, K, st);
+    return pw_dgrad_rows(a, b, ep_bnbwd<EpStoreBnBwdT<E>>(ep, part, bn_x, bn), M, C, K, st);
+  }
+  const EpWidenT<E> ep = ep_widen(dx, C, OH, OW, stride, residual);  // (the entries refuse a residual next to part)
+  if (!part) return pw_dgrad_rows(a, b, ep, M, C, K, st);
+  return pw_dgrad_rows(a, b, ep_bnbwd<EpWidenBnBwdT<E>>(ep, part, bn_x, bn), M, C, K, st);
+}
+
+// The tiled tail of dk_pwconv_dgrad_bnbwd_*: a = (g, bn_x) with the following BatchNorm's backward on
+// load; dx = dy . W (+ residual) and, with part, the input BatchNorm's backward partials over (dx, x).
+template <class E>
+static int pw_dgrad_bnbwd_tail(const MatBwdDescE<E>& a, int M, int K, const float* w_kc, int C, E* dx,
+                               const E* residual, const E* x, const BnIn& bn, double* part, hipStream_t st) {
+  const MatDesc b = mat(w_kc, K, C, C);
+  const EpStoreT<E> ep = ep_store(dx, C, nullptr, residual);
+  if (!part) return igemm_rows<LdMatKC, LdMatIC>(a, b, ep, M, C, K, kRowBnBwd, st);
+  return igemm_rows<LdMatKC, LdMatIC>(a, b, ep_bnbwd<EpStoreBnBwdT<E>>(ep, part, x, bn), M, C, K, kRowBnBwd, st);
+}
+
+// Weight gradient through the split-K engine: slabs = a^T . im2col(x) over the pixels, then the
+// fixed-order reduce (+ l2 * w) into the KCRS (mode 1) or [K][C] (mode 0) layout.
+template <template <int, int, int> class LA, class DA, class D>
+static int splitk_wgrad(const DA& a, const D& b, int K, int Ncol, const float* w, float l2, float* dw, int mode, int C,
+                        int Cp, int R, int S, void* ws, hipStream_t st) {
   int splits = 1;
   float* part = static_cast<float*>(ws);
-  const hipStream_t st = as_stream(stream);
-  int rc = vec_ok(a, 4, K) ? igemm_splitk<LdMatIC, MatDesc, LdImgIC, D>(a, b, part, K, Ncol, Kred, st, &splits)
-                           : igemm_splitk<LdMatIC1, MatDesc, LdImgIC, D>(a, b, part, K, Ncol, Kred, st, &splits);
+  const int rc = igemm_splitk<LA, LdImgIC>(a, b, part, K, Ncol, b.M, st, &splits);
   if (rc) return rc;
   return splitk_reduce(part, splits, K, Ncol, dw, w, l2, mode, C, Cp, R, S, st);
+}
+// dw[k][c][r][s] = sum_{n,oh,ow} dy[n,oh,ow,k] * x[n, oh*stride + r - pad, ow*stride + s - pad, c]  (+ l2 * w);
+// b = the view of x (or of bn(x)).  The split rule is the one of dy's element type.
+template <class E, class D>
+static int wgrad(const E* dy, const D& b, int K, int Ncol, const float* w, float l2, float* dw, int mode, int C,
+                 int Cp, int R, int S, void* ws, size_t ws_bytes, void* stream) {
+  const int Kred = b.M;
+  if (!fits((size_t)Kred * K * 4)) return DK_ERR_ARGS;  // (before the workspace: callers see this order)
+  if (ws_bytes < splitk_ws_bytes(K, Ncol, Kred, kMfOf<E>)) return DK_ERR_WORKSPACE;
+  const MatDescE<E> a = mat(dy, Kred, K, K);
+  if constexpr (std::is_same<E, float>::value) {
+    if (!vec_ok(a, 4, K))  // the scalar loader of dy (the bf16 entries refuse what needs it)
+      return splitk_wgrad<LdMatIC1>(a, b, K, Ncol, w, l2, dw, mode, C, Cp, R, S, ws, as_stream(stream));
+  }
+  return splitk_wgrad<LdMatIC>(a, b, K, Ncol, w, l2, dw, mode, C, Cp, R, S, ws, as_stream(stream));
 }
 
 // Weight gradient with the following BatchNorm's backward applied as dy is loaded: g is the
@@ -1463,7 +1588,7 @@ static int wgrad(const float* dy, const D& b, int K, int Ncol, const float* w, f
 // k12 its parameters and folded coefficients -- dy = dk_bn_bwd_apply_f32(bn_x, g) bit for bit,
 // never stored (the stem, whose input gradient is not needed: the apply pass over its
 // 64 x 112 x 112 output per image and the re-read of dy become one read of g and bn_x).
-// bn_* (optional): this layer's input BatchNorm applied on load, as dk_conv2d_wgrad_bnx_f32.
+// b may carry this layer's input BatchNorm, as dk_conv2d_wgrad_bnx_f32.
 template <class D>
 static int wgrad_bnbwd(const float* g, const float* bn_x, const D& b, int K, int Ncol, const BnBwdIn& bw,
                        const float* w, float l2, float* dw, int C, int Cp, int R, int S, void* ws, size_t ws_bytes,
@@ -1471,19 +1596,10 @@ static int wgrad_bnbwd(const float* g, const float* bn_x, const D& b, int K, int
   const int Kred = b.M;
   if (!fits((size_t)Kred * K * 4)) return DK_ERR_ARGS;
   if (ws_bytes < splitk_ws_bytes(K, Ncol, Kred)) return DK_ERR_WORKSPACE;
-  MatDesc a0 = mat(g, Kred, K, K);
-  if (!vec_ok(a0, 4, K) || !aligned16(bn_x)) return DK_ERR_ARGS;
-  MatBwdDesc a;
-  static_cast<MatDesc&>(a) = a0;
-  a.x = bn_x;
-  a.bwd = bw;
-  a.dy_out = nullptr;
-  int splits = 1;
-  float* part = static_cast<float*>(ws);
-  const hipStream_t st = as_stream(stream);
-  int rc = igemm_splitk<LdMatIC, MatBwdDesc, LdImgIC, D>(a, b, part, K, Ncol, Kred, st, &splits);
-  if (rc) return rc;
-  return splitk_reduce(part, splits, K, Ncol, dw, w, l2, 1, C, Cp, R, S, st);
+  const MatDesc a = mat(g, Kred, K, K);
+  if (!vec_ok(a, 4, K) || !aligned16(bn_x)) return DK_ERR_ARGS;  // (after the workspace: callers see this order)
+  return splitk_wgrad<LdMatIC>(with_bnbwd(a, bn_x, bw, static_cast<float*>(nullptr)), b, K, Ncol, w, l2, dw, 1, C, Cp, R,
+                               S, ws, as_stream(stream));
 }
 
 }  // namespace dk

@@ -33,15 +33,14 @@ DK_API int dk_pwconv_fwd_f32(const float* x, int N, int H, int W, int C, const f
       return pw_deep_fwd(x, N, H, W, stride, OH, OW, w_kc, K, C, bias, y, nullptr, nullptr, nullptr, nullptr, 0,
                          nullptr, deep, as_stream(stream));
   }
-  MatDesc b = mat(w_kc, K, C, K);
-  EpStore ep = ep_store(y, K, bias);
   if (C % 4 || !aligned16(x) || !aligned16(w_kc)) {
     // Unaligned channel count: scalar loads, stride 1 only (the rows are then a plain matrix).
     if (stride != 1) return DK_ERR_ARGS;
-    MatDesc a = mat(x, N * H * W, C, N * H * W);
-    return igemm_rows<LdMatKC1, MatDesc, LdMatKC1, MatDesc, EpStore>(a, b, ep, N * H * W, K, C, as_stream(stream));
+    return igemm_rows<LdMatKC1, LdMatKC1>(mat(x, N * H * W, C, N * H * W), mat(w_kc, K, C, K), ep_store(y, K, bias),
+                                          N * H * W, K, C, kRowPlain, as_stream(stream));
   }
-  return conv_fwd(img1(x, N, H, W, C, OH, OW, stride, N * OH * OW), w_kc, K, C, bias, y, stream);
+  return fwd_rows(img1(x, N, H, W, C, OH, OW, stride, N * OH * OW), w_kc, K, C, bias, y, nullptr, nullptr, nullptr,
+                  nullptr, 0, nullptr, kRowPlain, as_stream(stream));
 }
 
 // The same with x = the raw output of the previous layer and y = pw(bn(x)) (+ReLU inside).
@@ -50,10 +49,9 @@ DK_API int dk_pwconv_fwd_bnx_f32(const float* x, int N, int H, int W, int C, con
                                  const float* bn_invstd, const float* bn_gamma, const float* bn_beta, int bn_relu,
                                  void* stream) {
   if (C % 4 || !aligned16(x) || !aligned16(w_kc) || !fits((size_t)N * H * W * C * 4)) return DK_ERR_ARGS;
-  if (!bn_ok(bn_mean, bn_invstd, bn_gamma, bn_beta)) return DK_ERR_ARGS;
-  return conv_fwd(with_bn(img1(x, N, H, W, C, OH, OW, stride, N * OH * OW), bn_mean, bn_invstd, bn_gamma,
-                          bn_beta, bn_relu),
-                  w_kc, K, C, bias, y, stream);
+  if (!bn_mean) return DK_ERR_ARGS;  // (to the body NULL means no input BatchNorm)
+  return fwd_rows(img1(x, N, H, W, C, OH, OW, stride, N * OH * OW), w_kc, K, C, bias, y, bn_mean, bn_invstd, bn_gamma,
+                  bn_beta, bn_relu, nullptr, kRowPlain, as_stream(stream));
 }
 
 DK_API int dk_pwconv_fwd_stats_rows(int N, int OH, int OW, int K, int C) {
@@ -83,8 +81,9 @@ DK_API int dk_pwconv_fwd_ex_f32(const float* x, int N, int H, int W, int C, cons
       return pw_stream_fwd(x, N, H, W, stride, OH, OW, w_kc, K, bias, y, bn_mean, bn_invstd, bn_gamma, bn_beta,
                            bn_relu, stats, c.plan, as_stream(stream), ft);
     });
-  return conv_fwd_ex(img1(x, N, H, W, C, OH, OW, stride, N * OH * OW), w_kc, K, C, bias, y, bn_mean,
-                     bn_invstd, bn_gamma, bn_beta, bn_relu, stats, stream);
+  // kRowPlain: the fp32 pointwise forward picks its tile as a plain GEMM (the bf16 twin as kRowFwdH)
+  return fwd_rows(img1(x, N, H, W, C, OH, OW, stride, N * OH * OW), w_kc, K, C, bias, y, bn_mean, bn_invstd, bn_gamma,
+                  bn_beta, bn_relu, stats, kRowPlain, as_stream(stream));
 }
 
 // Pointwise dgrad (pointwise_convolution.py:65-72): dx_rows = dy_rows . W; for stride > 1 the
@@ -93,23 +92,14 @@ DK_API int dk_pwconv_dgrad_f32(const float* dy, int N, int OH, int OW, int K, co
                                float* dx, void* stream) {
   const int M = N * OH * OW;
   if (!fits((size_t)M * K * 4)) return DK_ERR_ARGS;
-  MatDesc a = mat(dy, M, K, M);
-  MatDesc b = mat(w_kc, K, C, C);
   const hipStream_t st = as_stream(stream);
-  const bool vec = vec_ok(a, K, 4) && vec_ok(b, 4, C);
-  if (stride == 1 && vec && aligned16(dy) && aligned16(w_kc) && aligned16(dx)) {
+  if (stride == 1 && vec_ok(mat(dy, M, K, M), K, 4) && vec_ok(mat(w_kc, K, C, C), 4, C) && aligned16(dy) &&
+      aligned16(w_kc) && aligned16(dx)) {
     // the deep dgrad kernel's plain form (pw_deep.hip): bit-identical dx (the skip projections)
     const PwPlan deep = pw_deep_dgrad_plan(M, K, C);
     if (deep.rows) return pw_deep_dgrad_plain(dy, M, K, C, w_kc, dx, deep, st);
   }
-  if (stride == 1) {
-    EpStore ep = ep_store(dx, C, nullptr);
-    if (vec) return igemm_rows<LdMatKC, MatDesc, LdMatIC, MatDesc, EpStore>(a, b, ep, M, C, K, st);
-    return igemm_rows<LdMatKC1, MatDesc, LdMatIC1, MatDesc, EpStore>(a, b, ep, M, C, K, st);
-  }
-  EpWiden ep = ep_widen(dx, C, OH, OW, stride);
-  if (vec) return igemm_rows<LdMatKC, MatDesc, LdMatIC, MatDesc, EpWiden>(a, b, ep, M, C, K, st);
-  return igemm_rows<LdMatKC1, MatDesc, LdMatIC1, MatDesc, EpWiden>(a, b, ep, M, C, K, st);
+  return pw_dgrad_tail<float>(dy, M, OH, OW, K, w_kc, C, stride, dx, nullptr, nullptr, BnIn{}, nullptr, st);
 }
 
 DK_API int dk_pwconv_dgrad_stats_rows(int N, int OH, int OW, int K, int C) { return stats_rows(N * OH * OW, C, K); }
@@ -129,40 +119,9 @@ DK_API int dk_pwconv_dgrad_ex_f32(const float* dy, int N, int OH, int OW, int K,
   if (!fits((size_t)M * K * 4) || (part != nullptr) != (bn_x != nullptr)) return DK_ERR_ARGS;
   if (part && (!bn_mean || !bn_invstd || !bn_gamma || !bn_beta)) return DK_ERR_ARGS;
   if (part && residual && stride != 1) return DK_ERR_ARGS;  // off-lattice residual terms would need reducing
-  MatDesc a = mat(dy, M, K, M);
-  MatDesc b = mat(w_kc, K, C, C);
-  const hipStream_t st = as_stream(stream);
-  const bool vec = vec_ok(a, K, 4) && vec_ok(b, 4, C);
-#define DK_ROWS(EPT, ep)                                                              \
-  return vec ? igemm_rows<LdMatKC, MatDesc, LdMatIC, MatDesc, EPT>(a, b, ep, M, C, K, st) \
-             : igemm_rows<LdMatKC1, MatDesc, LdMatIC1, MatDesc, EPT>(a, b, ep, M, C, K, st)
-  if (!part) {
-    if (stride == 1) {
-      EpStore ep = ep_store(dx, C, nullptr, residual);
-      DK_ROWS(EpStore, ep);
-    }
-    EpWiden ep = ep_widen(dx, C, OH, OW, stride, residual);
-    DK_ROWS(EpWiden, ep);
-  }
-  const BnIn bn{bn_mean, bn_invstd, bn_gamma, bn_beta, bn_relu};
-  const int xv4 = aligned16(bn_x) && bn_ok(bn_mean, bn_invstd, bn_gamma, bn_beta);
-  if (stride == 1) {
-    EpStoreBnBwd ep;
-    static_cast<EpStore&>(ep) = ep_store(dx, C, nullptr, residual);
-    ep.v4 = ep.v4 && xv4;
-    ep.part = part;
-    ep.xbn = bn_x;
-    ep.bn = bn;
-    DK_ROWS(EpStoreBnBwd, ep);
-  }
-  EpWidenBnBwd ep;
-  static_cast<EpWiden&>(ep) = ep_widen(dx, C, OH, OW, stride);
-  ep.v4 = ep.v4 && xv4;
-  ep.part = part;
-  ep.xbn = bn_x;
-  ep.bn = bn;
-  DK_ROWS(EpWidenBnBwd, ep);
-#undef DK_ROWS
+  // (any alignment of bn_x and of the BN vectors is taken: v4 drops to the scalar partial loads)
+  return pw_dgrad_tail(dy, M, OH, OW, K, w_kc, C, stride, dx, residual, bn_x,
+                       BnIn{bn_mean, bn_invstd, bn_gamma, bn_beta, bn_relu}, part, as_stream(stream));
 }
 
 // dk_pwconv_dgrad_ex_f32 with the input BN's partials for stride > 1, the widened gradient kept
@@ -176,18 +135,10 @@ DK_API int dk_pwconv_dgrad_lattice_f32(const float* dy, int N, int OH, int OW, i
   if (!fits((size_t)M * K * 4) || !fits((size_t)M * C * 4) || stride < 2 || !dx_lat || !bn_x || !part)
     return DK_ERR_ARGS;
   if (!bn_mean || !bn_invstd || !bn_gamma || !bn_beta) return DK_ERR_ARGS;
-  MatDesc a = mat(dy, M, K, M);
-  MatDesc b = mat(w_kc, K, C, C);
-  const hipStream_t st = as_stream(stream);
-  const bool vec = vec_ok(a, K, 4) && vec_ok(b, 4, C);
-  EpLatticeBnBwd ep;
-  static_cast<EpWiden&>(ep) = ep_widen(dx_lat, C, OH, OW, stride);
-  ep.v4 = ep.v4 && aligned16(bn_x) && bn_ok(bn_mean, bn_invstd, bn_gamma, bn_beta);
-  ep.part = part;
-  ep.xbn = bn_x;
-  ep.bn = BnIn{bn_mean, bn_invstd, bn_gamma, bn_beta, bn_relu};
-  return vec ? igemm_rows<LdMatKC, MatDesc, LdMatIC, MatDesc, EpLatticeBnBwd>(a, b, ep, M, C, K, st)
-             : igemm_rows<LdMatKC1, MatDesc, LdMatIC1, MatDesc, EpLatticeBnBwd>(a, b, ep, M, C, K, st);
+  const BnIn bn{bn_mean, bn_invstd, bn_gamma, bn_beta, bn_relu};
+  return pw_dgrad_rows(mat(dy, M, K, M), mat(w_kc, K, C, C),
+                       ep_bnbwd<EpLatticeBnBwd>(ep_widen(dx_lat, C, OH, OW, stride), part, bn_x, bn), M, C, K,
+                       as_stream(stream));
 }
 
 // dgrad of a stride-1 pointwise layer whose output fed a BatchNorm (+ReLU), with that BN's
@@ -207,15 +158,9 @@ DK_API int dk_pwconv_dgrad_bnbwd_f32(const float* g, const float* bn_x, int N, i
   if (!fits((size_t)M * K * 4) || (part != nullptr) != (x != nullptr)) return DK_ERR_ARGS;
   if (part && (!bn_mean || !bn_invstd || !bn_gamma || !bn_beta)) return DK_ERR_ARGS;
   if (!out_mean || !out_invstd || !out_gamma || !out_beta || !k12 || !bn_x) return DK_ERR_ARGS;
-  MatBwdDesc a;
-  static_cast<MatDesc&>(a) = mat(g, M, K, M);
-  a.x = bn_x;
-  a.bwd = BnBwdIn{out_mean, out_invstd, out_gamma, out_beta, k12, out_relu, K};
-  a.dy_out = dy_out;
-  MatDesc b = mat(w_kc, K, C, C);
   const hipStream_t st = as_stream(stream);
   // 16-byte loads of g, bn_x and dy_out; the LDS table holds 2 float4 per channel
-  if (!vec_ok(b, 4, C) || K % 4 || !aligned16(g) || !aligned16(bn_x) || (dy_out && !aligned16(dy_out)) ||
+  if (!vec_ok(mat(w_kc, K, C, C), 4, C) || K % 4 || !aligned16(g) || !aligned16(bn_x) || (dy_out && !aligned16(dy_out)) ||
       (size_t)K * 32 > 64 * 1024)
     return DK_ERR_ARGS;
   const PwChoice c = pw_dgrad_choice(M, K, C);
@@ -234,21 +179,14 @@ DK_API int dk_pwconv_dgrad_bnbwd_f32(const float* g, const float* bn_x, int N, i
                                    part, c.plan, st, ft);
     });
   }
-  if (!part) {
-    EpStore ep = ep_store(dx, C, nullptr, residual);
-    return igemm_rows<LdMatKC, MatBwdDesc, LdMatIC, MatDesc, EpStore, kRowBnBwd>(a, b, ep, M, C, K, st);
-  }
-  EpStoreBnBwd ep;
-  static_cast<EpStore&>(ep) = ep_store(dx, C, nullptr, residual);
-  ep.v4 = ep.v4 && aligned16(x) && bn_ok(bn_mean, bn_invstd, bn_gamma, bn_beta);
-  ep.part = part;
-  ep.xbn = x;
-  ep.bn = BnIn{bn_mean, bn_invstd, bn_gamma, bn_beta, bn_relu};
-  return igemm_rows<LdMatKC, MatBwdDesc, LdMatIC, MatDesc, EpStoreBnBwd, kRowBnBwd>(a, b, ep, M, C, K, st);
+  // (with part, any alignment of x and of the BN vectors is taken: v4 drops to the scalar partial loads)
+  return pw_dgrad_bnbwd_tail(
+      with_bnbwd(mat(g, M, K, M), bn_x, BnBwdIn{out_mean, out_invstd, out_gamma, out_beta, k12, out_relu, K}, dy_out), M, K,
+      w_kc, C, dx, residual, x, BnIn{bn_mean, bn_invstd, bn_gamma, bn_beta, bn_relu}, part, st);
 }
 
 DK_API size_t dk_pwconv_wgrad_workspace_bytes(int N, int OH, int OW, int K, int C) {
-  // (the bf16 twin's tiles can differ: the larger of the two)
+  // (one query for both dtypes' entries; the bf16 twin's tiles can differ: the larger of the two needs)
   const int M = N * OH * OW;
   size_t a = splitk_ws_bytes(K, C, M), b = splitk_ws_bytes(K, C, M, kMfBf16);
   if (a < b) a = b;
@@ -271,7 +209,6 @@ DK_API int dk_pwconv_wgrad_bnx_f32(const float* dy, const float* x, int N, int H
                                    const float* bn_gamma, const float* bn_beta, int bn_relu, void* stream) {
   if (C % 4 || !aligned16(x) || !fits((size_t)N * H * W * C * 4)) return DK_ERR_ARGS;
   if (!bn_ok(bn_mean, bn_invstd, bn_gamma, bn_beta)) return DK_ERR_ARGS;
-  const int M = N * OH * OW;
   return wgrad(dy,
                with_bn(img(x, N, H, W, C, OH, OW, 1, 1, stride, 1, 0, N * OH * OW), bn_mean, bn_invstd, bn_gamma,
                        bn_beta, bn_relu),

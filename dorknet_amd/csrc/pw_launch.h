@@ -22,7 +22,6 @@ inline int min_occupancy(const void* const* fs, int n, int threads) {
   return o;
 }
 
-constexpr int kPwCUs = 256;  // compute units the persistent grids are sized for
 
 // Blocks of a streaming grid (WAVES waves per block, each walking TR-pixel tiles): every resident
 // slot once, at most one block per WAVES tiles.  A function of its arguments only, so the row count
@@ -30,7 +29,7 @@ constexpr int kPwCUs = 256;  // compute units the persistent grids are sized for
 inline int pw_stream_grid(int M, int TR, int WAVES, int occ) {
   const int ntiles = (M + TR - 1) / TR;
   const int want = (ntiles + WAVES - 1) / WAVES;
-  const int slots = occ * kPwCUs;
+  const int slots = occ * kNumCUs;
   return want < slots ? (want > 0 ? want : 1) : slots;
 }
 
@@ -43,7 +42,7 @@ inline int pw_stream_grid(int M, int TR, int WAVES, int occ) {
 inline int pw_deep_grid(int M, int N, int NB, int tr, int occ) {
   const int ntiles = (M + tr - 1) / tr;
   const int groups = N < NB ? 1 : N / NB;
-  int slots = occ * kPwCUs / groups;
+  int slots = occ * kNumCUs / groups;
   if (slots < 1) slots = 1;
   int gx = ntiles < slots ? ntiles : slots;
   const int g8 = gx / 8 * 8;

@@ -105,6 +105,10 @@ CASES = {
     19: (24, 40, 2, 2, 13, 9),
     20: (16, 3, 1, 3, 13, 11),      # C % 4 != 0: scalar loaders of the plain entry points; the others refuse
     21: (16, 3, 1, 1, 1, 33),
+    22: (16, 3, 2, 2, 13, 9),       # the scalar loaders under the widening and the lattice epilogues
+    23: (132, 6, 1, 2, 9, 9),       # ... and with a reduction past 128 (the deeper k-tile), 162 pixels
+    24: (132, 6, 2, 2, 13, 9),
+    25: (512, 512, 2, 2, 9, 9),     # bf16 strided forward on the tiled engine's 128 x 128, 8-wave tile; 50 pixels
 }
 
 # The seed of each case: the first of 0, 1, 2, ... at which mask_margin > 1 holds for the input BatchNorm (on x

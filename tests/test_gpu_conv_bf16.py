@@ -53,6 +53,13 @@ SHAPES = {
     "4x4s2": (2, 8, 8, 13, 11, 24, 4, 4, 2, 1),
     "5x5s2_c3": (3, 3, 4, 9, 9, 8, 5, 5, 2, 2),      # the 4 stored channels are a padded C = 3
     "3x3s1_deep": (2, 72, 72, 7, 7, 136, 3, 3, 1, 1),  # k-tiles cross tap boundaries; > 2 column tiles
+    # 162 pixels (ragged for 64- and 128-pixel tiles), one shape per row tile the bf16 rule picks and the
+    # other shapes do not reach: short reduction with > 64 columns (64x64x16: this forward, wide_c's dgrads),
+    # long reduction with < 128 columns (128x64x32: wide_c's forward with statistics or BN on load), and
+    # 128 columns with a long reduction in the dgrads and with statistics (128x128x32, 8 waves)
+    "wide_k": (2, 8, 8, 9, 9, 72, 3, 3, 1, 1),
+    "wide_c": (2, 72, 72, 9, 9, 8, 3, 3, 1, 1),
+    "c128": (2, 128, 128, 9, 9, 128, 3, 3, 1, 1),
 }
 NAMES = list(SHAPES)
 
@@ -261,19 +268,19 @@ def test_bad_arguments_are_refused():
                                       *z, stream_handle())
 
 
-@pytest.mark.parametrize("shape", ["3x3s1", "many_tiles"])
+@pytest.mark.parametrize("shape", ["3x3s1", "many_tiles", "wide_k", "wide_k+bn", "wide_c", "c128"])
 def test_statistics_rows(shape):
     """part has rows + 1 NaN rows: the entry writes exactly dk_conv2d_fwd_bf16_stats_rows() rows, and
     they sum to the statistics of the stored output within one bf16 rounding per element -- either
     statistics rule (fp32 accumulator or stored value; the entry takes the stored value) passes, a
     missing or doubled row does not."""
-    if shape == "3x3s1":
-        name = shape
+    name, _, bn = shape.partition("+")  # "+bn": the same forward with the input BatchNorm on load
+    if name in SHAPES:
         N, C, Cp, H, W, K, R, S, st, pad = SHAPES[name]
         OH, OW = out_hw(name)
         rows = lib.dk_conv2d_fwd_bf16_stats_rows(N, OH, OW, K, Cp, R, S)
         part = torch.full((rows + 1, 2, K), float("nan"), dtype=torch.float64, device="cuda")
-        y = run_fwd(name, None, True, part)
+        y = run_fwd(name, 0 if bn else None, True, part)
     else:
         N, C, H, W, K = 4, 8, 40, 40, 24
         rng = np.random.RandomState(7)

@@ -170,8 +170,10 @@ def test_pointwise_layer(case):
     run_layer(layer, X, dY)
 
 
+# the last two: at most 64 inputs and more than 128 outputs (the weight gradient's 64x128 split-K tile, the
+# input gradient's deeper k-tile), on the 16-byte loaders and, with 62 and 130, on the scalar ones
 @pytest.mark.parametrize("case", [(4, 512, 120, True, 1e-4), (7, 128, 10, True, 5e-4), (3, 20, 33, False, 0.0),
-                                  (256, 512, 120, True, 1e-4)])
+                                  (256, 512, 120, True, 1e-4), (65, 64, 132, True, 1e-4), (65, 62, 130, False, 0.0)])
 def test_dense_layer(case):
     from dorknet_amd.layers.dense_layer import DenseLayer
     from dorknet_amd.regularisers.l2 import l2

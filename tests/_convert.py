@@ -111,7 +111,7 @@ def log_slack(name, err, want64, want32):
 
 def log_ratio(name, ratio, tag="dw"):
     """With DORKNET_SLACK_LOG=<file>: append "tag<TAB>name<TAB>worst err / bound" for a per-element check
-    (tests/_dw_ref.py:check; tag "dw" the depthwise, "pw" the pointwise, "conv" the dense-convolution, "bn" the BatchNorm family)
+    (tests/_dw_ref.py:check; tag "dw" the depthwise, "pw" the pointwise, "conv" the dense-convolution, "bn" the BatchNorm, "head" the classifier-head family)
     -- a recorded result, not a tolerance; log_slack's lines are the normwise tests'."""
     import os
     path = os.environ.get("DORKNET_SLACK_LOG")

@@ -269,7 +269,7 @@ def test_relu_gap_softmax():
     check("softmax test-mode", Pt, Po)
 
 
-@pytest.mark.parametrize("B,K", [(6, 120), (300, 12), (257, 10), (3, 130), (256, 128), (1, 4)])
+@pytest.mark.parametrize("B,K", [(6, 120), (300, 12), (257, 10), (3, 130), (256, 128), (1, 4), (17, 130), (5, 3)])
 def test_softmax_xent_shapes(B, K):
     """The head's softmax + cross-entropy forward on each of its paths: float4 rows (K % 4 == 0,
     K <= 128), scalar columns (K % 4 != 0), one wave per row (K > 128), and more than one 256-row
@@ -286,18 +286,20 @@ def test_softmax_xent_shapes(B, K):
     check("softmax bwd", sm.backward(), ref.softmax_xent_backward(Po, y.astype(np.float64)))
 
 
-@pytest.mark.parametrize("N,C,H", [(2, 8, 5), (3, 6, 7), (4, 512, 7), (2, 64, 3)])
+@pytest.mark.parametrize("N,C,H", [(2, 8, 5), (3, 6, 7), (4, 512, 7), (2, 64, 3), (3, 20, 2), (2, 8, (2, 4))])
 def test_gap_shapes(N, C, H):
-    """Global average pooling forward (loads issued eight at a time, HW = 9 / 25 / 49 with a remainder)
-    and backward (float4 for C % 4 == 0, scalar otherwise) against the oracle (pooling.py:23-36)."""
+    """Global average pooling forward (loads issued eight at a time, HW = 9 / 25 / 49 with a remainder, HW = 4
+    the remainder alone, H x W = 2 x 4 = 8 without one) and backward (float4 for C % 4 == 0, scalar otherwise)
+    against the oracle (pooling.py:23-36).  H: the side of a square map, or (H, W)."""
     from dorknet_amd.layers.pooling import GlobalAveragePoolingLayer
+    H, W = H if isinstance(H, tuple) else (H, H)
     rng = np.random.RandomState(N * C + H)
-    X = rng.randn(N, C, H, H).astype(np.float32)
+    X = rng.randn(N, C, H, W).astype(np.float32)
     gap = GlobalAveragePoolingLayer("g")
     gap.to_gpu()
     check("gap fwd", gap.forward(dev(X)), ref.gap_forward(X.astype(np.float64)))
     dG = rng.randn(N, C).astype(np.float32)
-    check("gap bwd", gap.backward(dev(dG)), ref.gap_backward(dG.astype(np.float64), (H, H)))
+    check("gap bwd", gap.backward(dev(dG)), ref.gap_backward(dG.astype(np.float64), (H, W)))
 
 
 def test_residual_block_and_sgd():

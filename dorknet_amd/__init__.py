@@ -17,7 +17,7 @@ __version__ = "0.1.0"
 _ALIASES = [
     "layers", "layers.layer", "layers.convolution", "layers.depthwise_convolution",
     "layers.pointwise_convolution", "layers.dense_layer", "layers.batch_norm", "layers.activations",
-    "layers.residual_block", "layers.pooling", "layers.reshape", "layers.losses",
+    "layers.residual_block", "layers.pooling", "layers.reshape", "layers.dropout", "layers.losses",
     "network", "network.feed_forward_network",
     "optimisers", "optimisers.SGDMomentum", "optimisers.SGD", "optimisers.RMSProp",
     "regularisers", "regularisers.l2",

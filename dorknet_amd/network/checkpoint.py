@@ -11,7 +11,8 @@ extension), layers/losses.py:36-42, layers/residual_block.py:99-151) and
 Layout (one HDF5 file per network, every layer's objects under its ``layer_name``):
 
 - ``<name>/layer_info``: an empty float32 dataset whose attributes describe the layer
-  (``type`` = class name, plus the constructor's shape / stride / padding / bias fields);
+  (``type`` = class name, plus the constructor's shape / stride / padding / bias fields; for the
+  extension ``DropoutLayer`` its ``drop_prob``, ``seed`` and the ``step`` of its next mask);
 - ``<name>/weights`` and ``<name>/bias`` (conv, depthwise, pointwise, dense), or
   ``<name>/gamma``, ``<name>/beta``, ``<name>/running_mean``, ``<name>/running_std`` (BN);
 - ``<name>/grads/<param>`` when ``save_grads`` (the default);
@@ -308,20 +309,39 @@ def _load_reshape(layer, open_f, load_grads):
                       tuple(int(v) for v in np.asarray(a["output_shape"]).ravel()))
 
 
+def _save_dropout(layer, open_f, save_grads):
+    """An extension (the reference has no dropout).  `step` is part of the state: a network saved after k
+    training forwards and reloaded draws the mask of step k next."""
+    d = _info(open_f, layer)
+    d.attrs["drop_prob"] = float(layer.drop_prob)
+    d.attrs["seed"] = np.int64(layer.seed)
+    d.attrs["step"] = np.int64(layer.step)
+
+
+def _load_dropout(layer, open_f, load_grads):
+    from ..layers.dropout import checked_count, checked_prob
+    a = _attrs(open_f, layer)
+    layer.drop_prob = checked_prob(layer.layer_name, float(a["drop_prob"]))
+    layer.seed = checked_count(layer.layer_name, "seed", int(a["seed"]))
+    layer.step = checked_count(layer.layer_name, "step", int(a["step"]))
+    layer._state = None
+
+
 def _new_layer(l_type, name):
     from ..layers.activations import ReLu
     from ..layers.batch_norm import BatchNormLayer
     from ..layers.convolution import ConvLayer
     from ..layers.dense_layer import DenseLayer
     from ..layers.depthwise_convolution import DepthwiseConvLayer
+    from ..layers.dropout import DropoutLayer
     from ..layers.losses import SoftmaxWithCrossEntropy
     from ..layers.pointwise_convolution import PointwiseConvLayer
     from ..layers.pooling import GlobalAveragePoolingLayer, MaxPoolLayer
     from ..layers.reshape import ReshapeLayer
     from ..layers.residual_block import ResidualBlock
     classes = {c.__name__: c for c in (ConvLayer, BatchNormLayer, ReLu, DepthwiseConvLayer, PointwiseConvLayer,
-                                       GlobalAveragePoolingLayer, MaxPoolLayer, ReshapeLayer, DenseLayer,
-                                       ResidualBlock, SoftmaxWithCrossEntropy)}
+                                       GlobalAveragePoolingLayer, MaxPoolLayer, ReshapeLayer, DropoutLayer,
+                                       DenseLayer, ResidualBlock, SoftmaxWithCrossEntropy)}
     if l_type not in classes:
         raise ValueError("unknown layer type {!r} for layer {!r}".format(l_type, name))
     return classes[l_type](name)
@@ -385,6 +405,7 @@ _HANDLERS = {
     "GlobalAveragePoolingLayer": (_save_plain, _load_plain),
     "MaxPoolLayer": (_save_maxpool, _load_maxpool),
     "ReshapeLayer": (_save_reshape, _load_reshape),
+    "DropoutLayer": (_save_dropout, _load_dropout),
     "SoftmaxWithCrossEntropy": (_save_plain, _load_plain),
     "ResidualBlock": (_save_residual, _load_residual),
 }

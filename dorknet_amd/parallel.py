@@ -128,6 +128,11 @@ class DataParallel:
                              "update_skip_projections={}: skip-projection gradients would be updated "
                              "without being all-reduced (or all-reduced for nothing)".format(
                                  update_skip_projections, opt_flag))
+        # one seed, a different dropout mask on every rank (layers/dropout.py)
+        from .layers.dropout import DropoutLayer
+        for l in _all_layers(network.layers):
+            if isinstance(l, DropoutLayer):
+                l.lane = dist.get_rank(group)
         if batch_norm == "sync":
             from .layers.batch_norm import BatchNormLayer
             for l in _all_layers(network.layers):

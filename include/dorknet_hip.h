@@ -602,6 +602,26 @@ int dk_flatten_fwd_bnx_f32(const float* x, int N, int HW, int C, const float* bn
 int dk_flatten_fwd_bnx_bf16(const uint16_t* x, int N, int HW, int C, const float* bn_mean, const float* bn_invstd, const float* bn_gamma, const float* bn_beta, int bn_relu, float* y, void* stream);
 int dk_flatten_bwd_f32(const float* dy, int N, int HW, int C, float* dx, void* stream);
 int dk_flatten_bwd_bf16(const float* dy, int N, int HW, int C, uint16_t* dx, void* stream);
+/* Dropout with a counter-based mask (an extension, layers/dropout.py; dorknet_amd/csrc/dropout.hip; DESIGN.md
+ * section 20).  Element k of the buffer has index i = first_index + k (storage order: NHWC bytes, row-major rows);
+ * block b = i >> 3 shares one Philox4x32-10 call with counter (b & 0xffffffff, b >> 32, step & 0xffffffff, lane) and
+ * key (seed & 0xffffffff, seed >> 32); with j = i & 7 the element's 16-bit field is output word j >> 1, low half for
+ * even j, high half for odd j.  The element is kept iff field >= threshold (= floor(p * 65536)).
+ *   dk_dropout_fwd_*: y = keep ? x * scale : +0.0 with scale = fp32(65536 / (65536 - threshold)), one fp32
+ *     rounding (bf16: the fp32 product rounded to nearest even once); a dropped element is +0.0 whatever x was.
+ *   dk_dropout_fwd_bnx_*: the same over BN(x) [+ ReLU] formed on load (see *_bnx_*; dk_bn_apply_*'s arithmetic,
+ *     for bf16 rounded to bf16 before the mask): bit-identical to apply-then-drop.  The channel of element k is k % C.
+ *   dk_dropout_bwd_*: dx = keep ? dy * scale : +0.0 from the same arguments: the mask is regenerated, not stored.
+ * Every output element is written exactly once.  16-byte accesses when x and y (and, for _bnx_, the parameters,
+ * with C % 4 == 0) are 16-byte aligned, element by element otherwise and on the n % 8 tail.
+ * DK_ERR_ARGS: a NULL tensor, n < 1, threshold outside 0..65535, seed, step or lane below 0, first_index below 0
+ * or no multiple of 8, C < 1 (_bnx_). */
+int dk_dropout_fwd_f32(const float* x, long long n, int threshold, long long seed, long long step, int lane, long long first_index, float* y, void* stream);
+int dk_dropout_fwd_bf16(const uint16_t* x, long long n, int threshold, long long seed, long long step, int lane, long long first_index, uint16_t* y, void* stream);
+int dk_dropout_fwd_bnx_f32(const float* x, long long n, int threshold, long long seed, long long step, int lane, long long first_index, int C, const float* bn_mean, const float* bn_invstd, const float* bn_gamma, const float* bn_beta, int bn_relu, float* y, void* stream);
+int dk_dropout_fwd_bnx_bf16(const uint16_t* x, long long n, int threshold, long long seed, long long step, int lane, long long first_index, int C, const float* bn_mean, const float* bn_invstd, const float* bn_gamma, const float* bn_beta, int bn_relu, uint16_t* y, void* stream);
+int dk_dropout_bwd_f32(const float* dy, long long n, int threshold, long long seed, long long step, int lane, long long first_index, float* dx, void* stream);
+int dk_dropout_bwd_bf16(const uint16_t* dy, long long n, int threshold, long long seed, long long step, int lane, long long first_index, uint16_t* dx, void* stream);
 int dk_softmax_xent_fwd_f32(const float* x, const float* y_onehot, int B, int K, float* p, float* loss, void* stream);
 int dk_softmax_xent_bwd_f32(const float* p, const float* y_onehot, int B, int K, float* dx, void* stream);
 

@@ -18,6 +18,10 @@ State file (``save_state_to_h5`` / ``load_state_from_h5``; its own file, not the
 a group ``optimiser`` with the attributes ``type`` (the class name), ``learning_rate``,
 ``momentum`` or ``decay_rate`` where the class has one, ``update_skip_projections``, and one fp32
 dataset ``optimiser/<layer_name>/<param>`` per state tensor, in the parameter's shape.
+
+Adam (optimisers/Adam.py) is built on the same base with a table row, a signature and state of its
+own: it overrides ``_init_state``, ``_entries``, ``_signature``, ``_build_table`` and
+``_state_items`` and names its integer attribute (``step_count``) in ``_COUNTERS``.
 """
 from __future__ import annotations
 
@@ -43,11 +47,12 @@ def discover_learnable_layers(network, update_skip_projections=False):
 
 
 class MultiTensorOptimiser:
-    """Base of SGD, SGDMomentum and RMSProp.  A subclass names its extra hyper-parameter in
+    """Base of SGD, SGDMomentum, RMSProp and Adam.  A subclass names its extra hyper-parameter in
     ``_HYPER`` (also the state file's attribute), says in ``_HAS_STATE`` whether it keeps a state
     tensor per parameter (``grad_cache``), and launches its kernel in ``_launch``."""
 
     _HYPER = ()
+    _COUNTERS = ()  # integer attributes of the state file (Adam's step_count)
     _HAS_STATE = True
     _STATE_WORDS = ("parameters, grads and state", "grad / state")
 
@@ -68,16 +73,24 @@ class MultiTensorOptimiser:
             pass
         self.learnable_layers = discover_learnable_layers(network, update_skip_projections)
         self.learning_rate = learning_rate
-        if self._HAS_STATE:
-            self.grad_cache = {}
-            for layer in self.learnable_layers:
-                layer_d = {}
-                for k, v in layer.grads.items():
-                    layer_d[k] = torch.zeros_like(v) if isinstance(v, torch.Tensor) else np.zeros_like(v)
-                self.grad_cache[layer] = layer_d
+        self._init_state()
         self._table = None
         self._table_sig = None
         self._total_blocks = 0
+
+    def _zero_state(self):
+        """{layer: {param: zeros shaped like the gradient}}"""
+        out = {}
+        for layer in self.learnable_layers:
+            layer_d = {}
+            for k, v in layer.grads.items():
+                layer_d[k] = torch.zeros_like(v) if isinstance(v, torch.Tensor) else np.zeros_like(v)
+            out[layer] = layer_d
+        return out
+
+    def _init_state(self):
+        if self._HAS_STATE:
+            self.grad_cache = self._zero_state()
 
     def set_learning_rate(self, new_lr):
         self.learning_rate = new_lr
@@ -119,30 +132,39 @@ class MultiTensorOptimiser:
     def _launch(self, table, ntens, total_blocks, stream):
         raise NotImplementedError
 
-    def update_weights(self):
-        entries = self._entries()
+    def _signature(self, entries):
+        if self._HAS_STATE:
+            return tuple((w.data_ptr(), g.data_ptr(), v.data_ptr(), w.numel()) for w, g, v in entries)
+        return tuple((w.data_ptr(), g.data_ptr(), 0, w.numel()) for w, g, _ in entries)
+
+    def _ensure_table(self, entries):
+        """Build the table at the first call and again only when a pointer or a size changed."""
         try:
-            if self._HAS_STATE:
-                sig = tuple((w.data_ptr(), g.data_ptr(), v.data_ptr(), w.numel()) for w, g, v in entries)
-            else:
-                sig = tuple((w.data_ptr(), g.data_ptr(), 0, w.numel()) for w, g, _ in entries)
+            sig = self._signature(entries)
         except AttributeError:  # host arrays: _build_table says what is wrong
             sig = None
         if sig is None or sig != self._table_sig:
             self._build_table(entries)
             self._table_sig = sig
+
+    def update_weights(self):
+        entries = self._entries()
+        self._ensure_table(entries)
         self._launch(self._table.data_ptr(), len(entries), self._total_blocks, stream_handle())
 
     # -- the state file -----------------------------------------------------------------------
 
-    def _state_items(self):
-        """[(dataset path, state tensor or array)], refusing layer names that would collide."""
+    def _check_layer_names(self):
         seen = set()
         for layer in self.learnable_layers:
             if layer.layer_name in seen:
                 raise ValueError("{}: two learnable layers are named {!r}; the state file keys its "
                                  "datasets by layer name".format(type(self).__name__, layer.layer_name))
             seen.add(layer.layer_name)
+
+    def _state_items(self):
+        """[(dataset path, state tensor or array)], refusing layer names that would collide."""
+        self._check_layer_names()
         if not self._HAS_STATE:
             return []
         return [("optimiser/{}/{}".format(layer.layer_name, k), v)
@@ -157,6 +179,8 @@ class MultiTensorOptimiser:
             g.attrs["learning_rate"] = np.float64(self.learning_rate)
             for h in self._HYPER:
                 g.attrs[h] = np.float64(getattr(self, h))
+            for h in self._COUNTERS:
+                g.attrs[h] = np.int64(getattr(self, h))
             g.attrs["update_skip_projections"] = bool(self.update_skip_projections)
             for path, v in items:
                 _write(f, path, v)
@@ -175,13 +199,14 @@ class MultiTensorOptimiser:
             stored = _as_str(attrs["type"]) if "type" in attrs else None
             if stored != name:
                 raise ValueError("{}: {} holds the state of a {}".format(name, fname, stored))
-            for h in ("learning_rate", *self._HYPER, "update_skip_projections"):
+            for h in ("learning_rate", *self._HYPER, *self._COUNTERS, "update_skip_projections"):
                 if h not in attrs:
                     raise ValueError("{}: {} has no attribute {!r}".format(name, fname, h))
             if bool(attrs["update_skip_projections"]) != bool(self.update_skip_projections):
                 raise ValueError("{}: {} was saved with update_skip_projections={}".format(
                     name, fname, bool(attrs["update_skip_projections"])))
             scalars = {h: float(attrs[h]) for h in ("learning_rate", *self._HYPER)}
+            scalars.update({h: int(attrs[h]) for h in self._COUNTERS})
             values = []
             for path, v in items:
                 if path not in f:

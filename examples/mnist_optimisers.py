@@ -1,8 +1,10 @@
-"""The three optimisers (reference: optimisers/SGD.py, optimisers/SGDMomentum.py, optimisers/RMSProp.py)
-on MNISTMaxPoolNet (examples/mnist_maxpool.py) over a fixed synthetic batch: U[0, 1) images with
+"""The reference's three optimisers (optimisers/SGD.py, optimisers/SGDMomentum.py, optimisers/RMSProp.py)
+and Adam (an extension; here with decoupled weight decay 0.01 and global-norm clipping at 5) on
+MNISTMaxPoolNet (examples/mnist_maxpool.py) over a fixed synthetic batch: U[0, 1) images with
 random labels, which the network memorises.  Prints the loss every few steps and, half way, saves
 the optimiser state (save_state_to_h5), builds a new optimiser and restores it (load_state_from_h5),
-so the run continues with the velocities / the squared-gradient cache it had.
+so the run continues with the velocities / the squared-gradient cache / the moments and step count
+it had.
 
     python examples/mnist_optimisers.py --optimiser rmsprop --steps 40
 """
@@ -27,6 +29,7 @@ def synthetic_batch(batch, seed=0):
 
 
 def make_optimiser(which, net, lr=None):
+    from dorknet_amd.optimisers.Adam import Adam
     from dorknet_amd.optimisers.RMSProp import RMSProp
     from dorknet_amd.optimisers.SGD import SGD
     from dorknet_amd.optimisers.SGDMomentum import SGDMomentum
@@ -34,6 +37,8 @@ def make_optimiser(which, net, lr=None):
         return SGD(net, 0.05 if lr is None else lr)
     if which == "sgdmomentum":
         return SGDMomentum(net, 0.01 if lr is None else lr, 0.9)
+    if which == "adam":
+        return Adam(net, 0.001 if lr is None else lr, weight_decay=0.01, max_grad_norm=5.0)
     return RMSProp(net, 0.001 if lr is None else lr, 0.9)
 
 
@@ -42,7 +47,7 @@ def main():
     import torch
     from dorknet_amd._tensor import as_device
     ap = argparse.ArgumentParser()
-    ap.add_argument("--optimiser", choices=["sgd", "sgdmomentum", "rmsprop"], default="rmsprop")
+    ap.add_argument("--optimiser", choices=["sgd", "sgdmomentum", "rmsprop", "adam"], default="rmsprop")
     ap.add_argument("--batch", type=int, default=64)
     ap.add_argument("--steps", type=int, default=40)
     ap.add_argument("--lr", type=float, default=None)

@@ -639,12 +639,37 @@ int dk_softmax_xent_bwd_f32(const float* p, const float* y_onehot, int B, int K,
  *                            d = ((-lr) * g) / sqrt(c + eps);  w = w + d;  c stored back
  *   (the reference's eps is 1e-5; one_minus_decay is 1 - decay formed in double by the caller).
  *   Both return DK_ERR_ARGS for a NULL table with ntens > 0 or a negative count.
+ *   Adam / AdamW (dorknet_amd/csrc/adam.hip; no optimiser of the reference: torch.optim.Adam / AdamW,
+ *   non-amsgrad, as single fp32 operations) has a table of its own, 56 bytes per entry:
+ *   { float* w; const float* g; float* m; float* v; int64 n; int64 first_block; int64 flags },
+ *   256 elements per block, flags bit 0 = apply keep (decoupled weight decay).  The caller forms in
+ *   double, with t the 1-based step number, omb1 = 1 - beta1, omb2 = 1 - beta2,
+ *   neg_step = -(lr / (1 - beta1^t)), sbc2 = sqrt(1 - beta2^t), keep = 1 - lr * weight_decay.
+ *   Per element, each operation rounded once to fp32, in this order:
+ *     dk_adam_multi_f32:     g' = s * g            (only with grad_scale, s = grad_scale[0]; else g' = g)
+ *                            w = keep * w          (only for flagged entries and keep != 1)
+ *                            m = beta1 * m + omb1 * g';  v = beta2 * v + omb2 * (g' * g')
+ *                            den = sqrt(v) / sbc2 + eps;  w = w + neg_step * (m / den)
+ *   g is read only, m, v and w are written once; grad_scale is a device pointer or NULL.  Argument
+ *   errors as above; ntens == 0 returns 0.
+ *   Global gradient norm and clipping: table entries { float* g; int64 n; int64 first_block }
+ *   (24 bytes), first_block = sum of ceil(n / 2048) over the preceding entries.
+ *     dk_grad_norm_multi_f32:  out[0] = (float)sqrt(sum g^2), the sum in fp64: one partial per block,
+ *                            added by one block in a fixed order (bit-identical from run to run);
+ *                            out[1] = min(1, max_norm / (out[0] + 1e-6f)), one fp32 rounding each
+ *                            (torch's clip_grad_norm_); max_norm <= 0 or infinite: out[1] = 1.
+ *                            ws: dk_grad_norm_workspace_bytes(total_blocks), else DK_ERR_WORKSPACE.
+ *     dk_grad_scale_multi_f32: g = scale[0] * g in place, one rounding; a scale of 1 writes nothing.
  *   l2 loss term: regularisers/l2.py:12-14; scale: l2.py:16-17 and DP averaging.
  *   colsum: bias gradients, np.sum(upstream_dx, axis=(0,2,3)) (convolution.py:91-92 etc.).
  * ------------------------------------------------------------------------------------- */
 int dk_sgd_momentum_multi_f32(const void* table, int ntens, long long total_blocks, float lr, float momentum, float grad_scale, void* stream);
 int dk_sgd_multi_f32(const void* table, int ntens, long long total_blocks, float lr, void* stream);
 int dk_rmsprop_multi_f32(const void* table, int ntens, long long total_blocks, float lr, float decay, float one_minus_decay, float eps, void* stream);
+int dk_adam_multi_f32(const void* table, int ntens, long long total_blocks, float beta1, float omb1, float beta2, float omb2, float neg_step, float sbc2, float eps, float keep, const float* grad_scale, void* stream);
+size_t dk_grad_norm_workspace_bytes(long long total_blocks);
+int dk_grad_norm_multi_f32(const void* table, int ntens, long long total_blocks, float max_norm, float* out, void* ws, size_t ws_bytes, void* stream);
+int dk_grad_scale_multi_f32(const void* table, int ntens, long long total_blocks, const float* scale, void* stream);
 int dk_l2_loss_f32(const float* w, long long n, float strength, int accumulate, float* out, void* stream);
 size_t dk_l2_multi_workspace_bytes(long long total_blocks);
 int dk_l2_loss_multi_f32(const void* table, int ntens, long long total_blocks, const float* add_to, float* out, void* ws, size_t ws_bytes, void* stream);

@@ -1,12 +1,13 @@
-"""update_weights of the three optimisers over ResNet-18-depsep's parameter set (104 tensors,
+"""update_weights of the optimisers over ResNet-18-depsep's parameter set (104 tensors,
 1,336,312 parameters; examples/resnet18_depsep.py): SGDMomentum (dk_sgd_momentum_multi_f32), SGD
-(dk_sgd_multi_f32) and RMSProp (dk_rmsprop_multi_f32), one multi-tensor launch each.  HIP events
-around --calls back-to-back update_weights() after a warm-up, --repeats times, the optimisers
-taking turns within a repeat; per call: the median over the repeats and their min-max.  Then the
-same for the C entry alone on the table update_weights() built (no Python walk over the tensors):
-back-to-back update_weights() calls are paced by the host, the entry alone by the launches.  All
-three share the network's parameters and gradients; the gradients are small, so the weights stay
-finite.
+(dk_sgd_multi_f32), RMSProp (dk_rmsprop_multi_f32) and Adam (dk_adam_multi_f32), one multi-tensor
+launch each, and Adam with max_grad_norm (the two launches of dk_grad_norm_multi_f32 before the
+update).  HIP events around --calls back-to-back update_weights() after a warm-up, --repeats times,
+the optimisers taking turns within a repeat; per call: the median over the repeats and their
+min-max.  Then the same for the C entries alone on the tables update_weights() built (no Python walk
+over the tensors): back-to-back update_weights() calls are paced by the host, the entries alone by
+the launches.  All share the network's parameters and gradients; the gradients are small, so the
+weights stay finite.
     python scripts/optimiser_bench.py [--calls 100] [--repeats 5]
 """
 import argparse
@@ -19,6 +20,8 @@ import numpy as np  # noqa: E402
 import torch  # noqa: E402
 
 from dorknet_amd._hip import stream_handle  # noqa: E402
+from dorknet_amd.optimisers.Adam import Adam  # noqa: E402
+from dorknet_amd.optimisers.clip import measure_grad_norm  # noqa: E402
 from dorknet_amd.optimisers.RMSProp import RMSProp  # noqa: E402
 from dorknet_amd.optimisers.SGD import SGD  # noqa: E402
 from dorknet_amd.optimisers.SGDMomentum import SGDMomentum  # noqa: E402
@@ -34,7 +37,8 @@ def main():
     net = ResNet18("bench")
     net.to_gpu()
     opts = [("SGDMomentum", SGDMomentum(net, 1e-4, 0.9)), ("SGD", SGD(net, 1e-4)),
-            ("RMSProp", RMSProp(net, 1e-6, 0.9))]
+            ("RMSProp", RMSProp(net, 1e-6, 0.9)), ("Adam", Adam(net, 1e-6, weight_decay=0.01)),
+            ("Adam+clip", Adam(net, 1e-6, weight_decay=0.01, max_grad_norm=1.0))]
     layers = opts[0][1].learnable_layers
     torch.manual_seed(0)
     for l in layers:
@@ -44,10 +48,14 @@ def main():
     nparam = sum(v.numel() for l in layers for v in l.learned_params.values())
     st = stream_handle()
 
-    def entry_only(opt):  # the C entry on the table update_weights built: the launch without the Python walk
-        opt._launch(opt._table.data_ptr(), ntens, opt._total_blocks, st)
+    def entry_only(opt):  # the C entries on the tables update_weights built: the launches without the Python walk
+        if getattr(opt, "max_grad_norm", None) is not None:
+            out = measure_grad_norm(opt, opt.max_grad_norm, unchanged=True)  # the cached table: no walk either
+            opt._launch(opt._table.data_ptr(), ntens, opt._total_blocks, st, out.data_ptr() + 4)
+        else:
+            opt._launch(opt._table.data_ptr(), ntens, opt._total_blocks, st)
 
-    for what, call in (("update_weights()", lambda opt: opt.update_weights()), ("the C entry alone", entry_only)):
+    for what, call in (("update_weights()", lambda opt: opt.update_weights()), ("the C entries alone", entry_only)):
         times = {name: [] for name, _ in opts}
         for r in range(a.repeats + 1):  # repeat 0 is the warm-up (and builds the tables)
             for name, opt in opts:

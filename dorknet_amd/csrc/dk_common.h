@@ -175,6 +175,16 @@ __device__ __forceinline__ double wave_sum(double v) {
   for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
   return v;
 }
+// Block-level (256 threads) sum of doubles through red[256] in LDS, a fixed tree; the result is in
+// red[0] (thread 0 reads it).
+__device__ __forceinline__ void block_sum(double* red, double s) {
+  red[threadIdx.x] = s;
+  __syncthreads();
+  for (int o = 128; o > 0; o >>= 1) {
+    if (threadIdx.x < o) red[threadIdx.x] += red[threadIdx.x + o];
+    __syncthreads();
+  }
+}
 
 // The BN output for one element (layers/batch_norm.py:91-96).  The standalone apply, the
 // backward ReLU-mask recompute and every consumer that applies a BN on load call this

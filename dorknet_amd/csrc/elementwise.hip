@@ -382,100 +382,8 @@ __global__ void softmax_xent_bwd_kernel(const float* __restrict__ p, const float
   dx[i] = (1.0f / (float)B) * (p[i] - y[i]);
 }
 
-// Multi-tensor optimiser updates: one launch over a table of tensors, one block per 256 elements.
-// The state pointer v is SGD momentum's velocity, RMSProp's squared-gradient cache, and unused
-// (null) for plain SGD.
-struct SgdEntry {
-  float* w;
-  const float* g;
-  float* v;
-  long long n;
-  long long block0;  // first block index owned by this tensor
-};
-
-constexpr int kSgdLdsTable = 1024;
-// The table entry owning this block and this thread's element index in it (>= e.n past the
-// tensor's end).  Called by all 256 threads of the block (it holds barriers).
-__device__ __forceinline__ long long multi_tensor_owner(const SgdEntry* __restrict__ tab, int ntens, SgdEntry& e) {
-  // find the tensor owning this block: the block0 column is loaded into LDS in parallel (one
-  // load latency) and searched there; the old linear scan of the global table was ~100
-  // dependent loads for the last blocks.
-  __shared__ long long b0s[kSgdLdsTable];
-  __shared__ int owner;
-  const long long b = blockIdx.x;
-  int t = 0;
-  if (ntens <= kSgdLdsTable) {
-    for (int i = threadIdx.x; i < ntens; i += blockDim.x) b0s[i] = tab[i].block0;
-    __syncthreads();
-    if (threadIdx.x == 0) {
-      int lo = 0, hi = ntens - 1;  // last entry with block0 <= b
-      while (lo < hi) {
-        const int mid = (lo + hi + 1) >> 1;
-        if (b0s[mid] <= b) lo = mid; else hi = mid - 1;
-      }
-      owner = lo;
-    }
-    __syncthreads();
-    t = owner;
-  } else {
-    while (t + 1 < ntens && tab[t + 1].block0 <= b) ++t;
-  }
-  e = tab[t];
-  return (b - e.block0) * 256 + threadIdx.x;
-}
-
-// SGD momentum: for every listed tensor t and element i
-//   d = (-lr) * g + mom * v;  w += d;  v = d      (SGDMomentum.py:33-39, same op order)
-__global__ __launch_bounds__(256) void sgd_momentum_multi_kernel(const SgdEntry* __restrict__ tab, int ntens,
-                                                                 float lr, float mom, float gscale) {
-  SgdEntry e;
-  const long long i = multi_tensor_owner(tab, ntens, e);
-  if (i >= e.n) return;
-  const float g = gscale == 1.0f ? e.g[i] : __fmul_rn(gscale, e.g[i]);
-  const float d = __fadd_rn(__fmul_rn(-lr, g), __fmul_rn(mom, e.v[i]));
-  e.w[i] = __fadd_rn(e.w[i], d);
-  e.v[i] = d;
-}
-
-// One fp32 operation, one rounding.  __fmul_rn / __fadd_rn are plain * and + compiled under the
-// default contraction mode, and once inlined a product and the sum it feeds may still fuse: plain
-// SGD's w + (-lr) * g came out as one v_fma_f32.  An operation compiled with contraction off
-// carries no contract flag and is never fused.
-__device__ __forceinline__ float mul_1r(float a, float b) {
-#pragma clang fp contract(off)
-  return a * b;
-}
-__device__ __forceinline__ float add_1r(float a, float b) {
-#pragma clang fp contract(off)
-  return a + b;
-}
-
-// Plain SGD:  d = (-lr) * g;  w += d      (SGD.py:20-24)
-__global__ __launch_bounds__(256) void sgd_multi_kernel(const SgdEntry* __restrict__ tab, int ntens, float lr) {
-  SgdEntry e;
-  const long long i = multi_tensor_owner(tab, ntens, e);
-  if (i >= e.n) return;
-  e.w[i] = add_1r(e.w[i], mul_1r(-lr, e.g[i]));
-}
-
-// RMSProp:  c = decay * c + (1 - decay) * (g * g);  d = ((-lr) * g) / sqrt(c + eps);  w += d
-// (RMSProp.py:28-36, same op order).  Every operation is one correctly rounded fp32 operation: no
-// contraction (above), sqrtf (v_sqrt_f32 plus its residual correction; __fsqrt_rn is the bare
-// 1-ulp instruction) and the full division sequence.
-__global__ __launch_bounds__(256) void rmsprop_multi_kernel(const SgdEntry* __restrict__ tab, int ntens, float lr,
-                                                            float decay, float one_minus_decay, float eps) {
-  SgdEntry e;
-  const long long i = multi_tensor_owner(tab, ntens, e);
-  if (i >= e.n) return;
-  const float g = e.g[i];
-  const float c = add_1r(mul_1r(decay, e.v[i]), mul_1r(one_minus_decay, mul_1r(g, g)));
-  const float d = __fdiv_rn(mul_1r(-lr, g), sqrtf(add_1r(c, eps)));
-  e.w[i] = add_1r(e.w[i], d);
-  e.v[i] = c;
-}
-
 // out[0] = 0.5 * strength * sum w^2 (one block, fp64 accumulate).  With accumulate != 0,
-// adds into out[0] instead of overwriting.
+// adds into out[0] instead of overwriting.  (All of a network's terms at once: multi_tensor.hip.)
 __global__ __launch_bounds__(256) void l2_loss_kernel(const float* __restrict__ w, long long n, float strength,
                                                       int accumulate, float* __restrict__ out) {
   __shared__ double red[256];
@@ -484,70 +392,11 @@ __global__ __launch_bounds__(256) void l2_loss_kernel(const float* __restrict__ 
     const double v = w[i];
     s += v * v;
   }
-  red[threadIdx.x] = s;
-  __syncthreads();
-  for (int o = 128; o > 0; o >>= 1) {
-    if (threadIdx.x < o) red[threadIdx.x] += red[threadIdx.x + o];
-    __syncthreads();
-  }
+  block_sum(red, s);
   if (threadIdx.x == 0) {
     const float v = (float)(0.5 * (double)strength * red[0]);
     out[0] = accumulate ? out[0] + v : v;
   }
-}
-
-// Multi-tensor l2 loss term, stage 1: block b (owning a 2048-element chunk of tensor t)
-// writes part[b] = 0.5 * strength_t * sum(w^2) over its chunk (fp64).
-struct L2Entry {
-  const float* w;
-  long long n;
-  long long block0;
-  float strength;
-  float pad_;
-};
-
-constexpr int kL2Chunk = 2048;
-
-__global__ __launch_bounds__(256) void l2_multi_partial_kernel(const L2Entry* __restrict__ tab, int ntens,
-                                                               double* __restrict__ part) {
-  __shared__ double red[256];
-  int t = 0;
-  const long long b = blockIdx.x;
-  while (t + 1 < ntens && tab[t + 1].block0 <= b) ++t;
-  const L2Entry e = tab[t];
-  const long long i0 = (b - e.block0) * kL2Chunk;
-  double s = 0.0;
-#pragma unroll
-  for (int k = 0; k < kL2Chunk / 256; ++k) {
-    const long long i = i0 + k * 256 + threadIdx.x;
-    if (i < e.n) {
-      const double v = e.w[i];
-      s += v * v;
-    }
-  }
-  red[threadIdx.x] = s;
-  __syncthreads();
-  for (int o = 128; o > 0; o >>= 1) {
-    if (threadIdx.x < o) red[threadIdx.x] += red[threadIdx.x + o];
-    __syncthreads();
-  }
-  if (threadIdx.x == 0) part[b] = 0.5 * (double)e.strength * red[0];
-}
-
-// Stage 2 (one block): out[0] = (add_to ? add_to[0] : 0) + sum_b part[b], fixed order.
-__global__ __launch_bounds__(256) void l2_multi_final_kernel(const double* __restrict__ part, long long nparts,
-                                                             const float* __restrict__ add_to,
-                                                             float* __restrict__ out) {
-  __shared__ double red[256];
-  double s = 0.0;
-  for (long long i = threadIdx.x; i < nparts; i += 256) s += part[i];
-  red[threadIdx.x] = s;
-  __syncthreads();
-  for (int o = 128; o > 0; o >>= 1) {
-    if (threadIdx.x < o) red[threadIdx.x] += red[threadIdx.x + o];
-    __syncthreads();
-  }
-  if (threadIdx.x == 0) out[0] = (float)((add_to ? (double)add_to[0] : 0.0) + red[0]);
 }
 
 // Column sums of an [M][N] matrix, stage 1: ws[chunk][n] = sum of rows in the chunk.
@@ -803,59 +652,8 @@ DK_API int dk_softmax_xent_bwd_f32(const float* p, const float* y_onehot, int B,
   return launch_status();
 }
 
-// table: device array of ntens SgdEntry records (40 bytes each, see include/dorknet_hip.h),
-// total_blocks = sum over tensors of ceil(n / 256) (== block0 of a virtual entry ntens).
-DK_API int dk_sgd_momentum_multi_f32(const void* table, int ntens, long long total_blocks, float lr, float momentum,
-                                     float grad_scale, void* stream) {
-  if (ntens <= 0) return 0;
-  hipLaunchKernelGGL(sgd_momentum_multi_kernel, dim3((unsigned)total_blocks), dim3(256), 0, as_stream(stream),
-                     static_cast<const SgdEntry*>(table), ntens, lr, momentum, grad_scale);
-  return launch_status();
-}
-
-// The same table for plain SGD (state pointer unused, 0) and RMSProp (state = the cache).
-static bool multi_args_ok(const void* table, int ntens, long long total_blocks) {
-  return ntens >= 0 && total_blocks >= 0 && total_blocks <= 0x7fffffffll && (table || ntens == 0);
-}
-
-DK_API int dk_sgd_multi_f32(const void* table, int ntens, long long total_blocks, float lr, void* stream) {
-  if (!multi_args_ok(table, ntens, total_blocks)) return DK_ERR_ARGS;
-  if (ntens == 0 || total_blocks == 0) return 0;
-  hipLaunchKernelGGL(sgd_multi_kernel, dim3((unsigned)total_blocks), dim3(256), 0, as_stream(stream),
-                     static_cast<const SgdEntry*>(table), ntens, lr);
-  return launch_status();
-}
-
-DK_API int dk_rmsprop_multi_f32(const void* table, int ntens, long long total_blocks, float lr, float decay,
-                                float one_minus_decay, float eps, void* stream) {
-  if (!multi_args_ok(table, ntens, total_blocks)) return DK_ERR_ARGS;
-  if (ntens == 0 || total_blocks == 0) return 0;
-  hipLaunchKernelGGL(rmsprop_multi_kernel, dim3((unsigned)total_blocks), dim3(256), 0, as_stream(stream),
-                     static_cast<const SgdEntry*>(table), ntens, lr, decay, one_minus_decay, eps);
-  return launch_status();
-}
-
 DK_API int dk_l2_loss_f32(const float* w, long long n, float strength, int accumulate, float* out, void* stream) {
   hipLaunchKernelGGL(l2_loss_kernel, dim3(1), dim3(256), 0, as_stream(stream), w, n, strength, accumulate, out);
-  return launch_status();
-}
-
-// All l2 loss terms of a network in two launches.  table: ntens L2Entry records (32 bytes:
-// { const float* w; int64 n; int64 first_block; float strength; float pad }), first_block =
-// sum of ceil(n / 2048) over the preceding entries, total_blocks = that sum over all.
-// out[0] = add_to[0] (may be null) + sum_t 0.5 * strength_t * sum(w_t^2).
-DK_API size_t dk_l2_multi_workspace_bytes(long long total_blocks) { return (size_t)total_blocks * sizeof(double); }
-
-DK_API int dk_l2_loss_multi_f32(const void* table, int ntens, long long total_blocks, const float* add_to,
-                                float* out, void* ws, size_t ws_bytes, void* stream) {
-  if (ntens <= 0 || total_blocks <= 0) return DK_ERR_ARGS;
-  if (ws_bytes < dk_l2_multi_workspace_bytes(total_blocks)) return DK_ERR_WORKSPACE;
-  hipLaunchKernelGGL(l2_multi_partial_kernel, dim3((unsigned)total_blocks), dim3(256), 0, as_stream(stream),
-                     static_cast<const L2Entry*>(table), ntens, static_cast<double*>(ws));
-  int rc = launch_status();
-  if (rc) return rc;
-  hipLaunchKernelGGL(l2_multi_final_kernel, dim3(1), dim3(256), 0, as_stream(stream), static_cast<const double*>(ws),
-                     total_blocks, add_to, out);
   return launch_status();
 }
 

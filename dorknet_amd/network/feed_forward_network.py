@@ -101,20 +101,16 @@ class FeedForwardNetwork:
         """loss_tensor + sum of 0.5*s*sum(W^2) over `plan` (dk_l2_loss_multi_f32)."""
         import torch
         from .._hip import lib, stream_handle, workspace
-        sig = tuple((w.data_ptr(), w.numel(), s) for w, s in plan)
-        if getattr(self, "_l2_sig", None) != sig:
-            rows, block0 = [], 0
-            for w, s in plan:
-                f = np.array([s, 0.0], dtype=np.float32).view(np.int64)[0]
-                rows.append((w.data_ptr(), w.numel(), block0, int(f)))
-                block0 += -(-w.numel() // 2048)
-            self._l2_table = torch.as_tensor(np.array(rows, dtype=np.int64).reshape(-1, 4), device="cuda")
-            self._l2_blocks = block0
-            self._l2_sig = sig
+        from .._table import DeviceTable, f32_word
+        t = getattr(self, "_l2_table", None)
+        if t is None:  # rows {w, n, first_block, strength}, 2048 elements per block
+            t = self._l2_table = DeviceTable(2048, "FeedForwardNetwork", ("l2-regularised weights", "weight"), 1,
+                                             hint="call forward after to_gpu()")
+        t.ensure([(w, f32_word(s)) for w, s in plan])
         out = torch.empty((), dtype=torch.float32, device=loss_tensor.device)
-        nb = lib.dk_l2_multi_workspace_bytes(self._l2_blocks)
-        lib.dk_l2_loss_multi_f32(self._l2_table.data_ptr(), len(plan), self._l2_blocks, loss_tensor.data_ptr(),
-                                 out.data_ptr(), workspace.get(nb), nb, stream_handle())
+        nb = lib.dk_l2_multi_workspace_bytes(t.blocks)
+        lib.dk_l2_loss_multi_f32(t.ptr, t.ntens, t.blocks, loss_tensor.data_ptr(), out.data_ptr(), workspace.get(nb),
+                                 nb, stream_handle())
         return out
 
     def forward(self, X, y_one_hot, test_mode=False, terminal_layer_name=None):

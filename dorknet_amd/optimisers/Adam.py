@@ -38,9 +38,6 @@ from __future__ import annotations
 
 import math
 
-import numpy as np
-import torch
-
 from .._hip import lib, stream_handle
 from ._multi import MultiTensorOptimiser
 from .clip import measure_grad_norm
@@ -55,7 +52,7 @@ def adam_scalars(learning_rate, beta1, beta2, weight_decay, t):
 class Adam(MultiTensorOptimiser):
     _HYPER = ("beta1", "beta2", "eps", "weight_decay")
     _COUNTERS = ("step_count",)
-    _HAS_STATE = False  # no grad_cache: the state is m and v
+    _POINTERS = 4  # w, g, m, v
     _STATE_WORDS = ("parameters, grads and moments", "grad / moment")
 
     def __init__(self, network, learning_rate, beta1=0.9, beta2=0.999, eps=1e-8, weight_decay=0.0,
@@ -84,29 +81,6 @@ class Adam(MultiTensorOptimiser):
                             self.v[layer][param], 1 if param in self.decay_params else 0))
         return out
 
-    def _signature(self, entries):
-        return tuple((w.data_ptr(), g.data_ptr(), m.data_ptr(), v.data_ptr(), w.numel(), flag)
-                     for w, g, m, v, flag in entries)
-
-    def _build_table(self, entries):
-        name = type(self).__name__
-        rows = []
-        block0 = 0
-        for w, g, m, v, flag in entries:
-            for t in (w, g, m, v):
-                if not (isinstance(t, torch.Tensor) and t.is_cuda and t.dtype == torch.float32
-                        and t.is_contiguous()):
-                    raise RuntimeError("{}: {} must be contiguous fp32 device tensors (build the optimiser "
-                                       "after network.to_gpu())".format(name, self._STATE_WORDS[0]))
-            n = w.numel()
-            if g.numel() != n or m.numel() != n or v.numel() != n:
-                raise ValueError("{}: {} size mismatch".format(name, self._STATE_WORDS[1]))
-            rows.append((w.data_ptr(), g.data_ptr(), m.data_ptr(), v.data_ptr(), n, block0, flag))
-            block0 += -(-n // 256)
-        table = np.array(rows, dtype=np.int64).reshape(-1, 7)
-        self._table = torch.as_tensor(table, device="cuda")
-        self._total_blocks = block0
-
     def _launch(self, table, ntens, total_blocks, stream, grad_scale=None):
         """The update for step number ``step_count`` (at least 1)."""
         omb1, omb2, neg_step, sbc2, keep = adam_scalars(self.learning_rate, self.beta1, self.beta2,
@@ -115,20 +89,20 @@ class Adam(MultiTensorOptimiser):
                               neg_step, sbc2, float(self.eps), keep, grad_scale, stream)
 
     def update_weights(self):
-        entries = self._entries()
-        self._ensure_table(entries)
+        t = self._dev
+        t.ensure(self._entries())
         grad_scale = None
         if self.max_grad_norm is not None:
             # the table's signature holds every gradient's pointer and size: while it is the one the
             # norm's table was last checked under, that table needs no second walk over the tensors
             st = getattr(self, "_clip_state", None)
             out = measure_grad_norm(self, self.max_grad_norm,
-                                    unchanged=st is not None and st.checked_under is self._table_sig)
-            self._clip_state.checked_under = self._table_sig
+                                    unchanged=st is not None and st.checked_under is t.sig)
+            self._clip_state.checked_under = t.sig
             self.last_grad_norm = out[0]
             grad_scale = out.data_ptr() + 4
         self.step_count += 1
-        self._launch(self._table.data_ptr(), len(entries), self._total_blocks, stream_handle(), grad_scale)
+        self._launch(t.ptr, t.ntens, t.blocks, stream_handle(), grad_scale)
 
     # -- the state file -----------------------------------------------------------------------
 

@@ -1,5 +1,5 @@
 """What the optimisers share: parameter discovery, the DataParallel flag handshake, the device
-table of the multi-tensor kernels (dorknet_amd/csrc/elementwise.hip) and the state file.
+table of the multi-tensor kernels (dorknet_amd/csrc/multi_tensor.hip) and the state file.
 
 Parameter discovery is the reference's SGDMomentum.py:7-14: every top-level layer with
 ``learned_params`` plus one level of ``layer_list``, skip projections only with
@@ -10,18 +10,18 @@ ResidualBlock is ever updated.  All three optimisers here use SGDMomentum's disc
 
 The table has one 40-byte row ``{w, g, state, n, first_block}`` per parameter tensor (``state``:
 the velocity or the squared-gradient cache, 0 for plain SGD), 256 elements per block.  It is
-built at the first ``update_weights`` and again only when a pointer or a size changes; the
-scalars travel as kernel arguments.  After that an update is one launch: no allocation, no host
-synchronisation.
+built (dorknet_amd/_table.py) at the first ``update_weights`` and again only when a pointer or a
+size changes; the scalars travel as kernel arguments.  After that an update is one launch: no
+allocation, no host synchronisation.
 
 State file (``save_state_to_h5`` / ``load_state_from_h5``; its own file, not the weights file):
 a group ``optimiser`` with the attributes ``type`` (the class name), ``learning_rate``,
 ``momentum`` or ``decay_rate`` where the class has one, ``update_skip_projections``, and one fp32
 dataset ``optimiser/<layer_name>/<param>`` per state tensor, in the parameter's shape.
 
-Adam (optimisers/Adam.py) is built on the same base with a table row, a signature and state of its
-own: it overrides ``_init_state``, ``_entries``, ``_signature``, ``_build_table`` and
-``_state_items`` and names its integer attribute (``step_count``) in ``_COUNTERS``.
+Adam (optimisers/Adam.py) is built on the same base with a wider row and state of its own: it
+overrides ``_init_state``, ``_entries`` and ``_state_items`` and names its integer attribute
+(``step_count``) in ``_COUNTERS``.
 """
 from __future__ import annotations
 
@@ -29,6 +29,7 @@ import numpy as np
 import torch
 
 from .._hip import stream_handle
+from .._table import DeviceTable
 
 
 def discover_learnable_layers(network, update_skip_projections=False):
@@ -49,11 +50,13 @@ def discover_learnable_layers(network, update_skip_projections=False):
 class MultiTensorOptimiser:
     """Base of SGD, SGDMomentum, RMSProp and Adam.  A subclass names its extra hyper-parameter in
     ``_HYPER`` (also the state file's attribute), says in ``_HAS_STATE`` whether it keeps a state
-    tensor per parameter (``grad_cache``), and launches its kernel in ``_launch``."""
+    tensor per parameter (``grad_cache``), and launches its kernel in ``_launch``.  ``_entries``
+    lists the table's rows: ``_POINTERS`` tensors each, then integer words (dorknet_amd/_table.py)."""
 
     _HYPER = ()
     _COUNTERS = ()  # integer attributes of the state file (Adam's step_count)
     _HAS_STATE = True
+    _POINTERS = 3  # w, g, state
     _STATE_WORDS = ("parameters, grads and state", "grad / state")
 
     def __init__(self, network, learning_rate, update_skip_projections=False):
@@ -74,9 +77,7 @@ class MultiTensorOptimiser:
         self.learnable_layers = discover_learnable_layers(network, update_skip_projections)
         self.learning_rate = learning_rate
         self._init_state()
-        self._table = None
-        self._table_sig = None
-        self._total_blocks = 0
+        self._dev = DeviceTable(256, name, self._STATE_WORDS, self._POINTERS)
 
     def _zero_state(self):
         """{layer: {param: zeros shaped like the gradient}}"""
@@ -110,47 +111,18 @@ class MultiTensorOptimiser:
                 out.append((w, g, v))
         return out
 
-    def _build_table(self, entries):
-        name = type(self).__name__
-        rows = []
-        block0 = 0
-        for w, g, v in entries:
-            for t in (w, g, v) if self._HAS_STATE else (w, g):
-                if not (isinstance(t, torch.Tensor) and t.is_cuda and t.dtype == torch.float32
-                        and t.is_contiguous()):
-                    raise RuntimeError("{}: {} must be contiguous fp32 device tensors (build the optimiser "
-                                       "after network.to_gpu())".format(name, self._STATE_WORDS[0]))
-            n = w.numel()
-            if g.numel() != n or (v is not None and v.numel() != n):
-                raise ValueError("{}: {} size mismatch".format(name, self._STATE_WORDS[1]))
-            rows.append((w.data_ptr(), g.data_ptr(), 0 if v is None else v.data_ptr(), n, block0))
-            block0 += -(-n // 256)
-        table = np.array(rows, dtype=np.int64).reshape(-1, 5)
-        self._table = torch.as_tensor(table, device="cuda")
-        self._total_blocks = block0
-
     def _launch(self, table, ntens, total_blocks, stream):
         raise NotImplementedError
 
-    def _signature(self, entries):
-        if self._HAS_STATE:
-            return tuple((w.data_ptr(), g.data_ptr(), v.data_ptr(), w.numel()) for w, g, v in entries)
-        return tuple((w.data_ptr(), g.data_ptr(), 0, w.numel()) for w, g, _ in entries)
-
-    def _ensure_table(self, entries):
-        """Build the table at the first call and again only when a pointer or a size changed."""
-        try:
-            sig = self._signature(entries)
-        except AttributeError:  # host arrays: _build_table says what is wrong
-            sig = None
-        if sig is None or sig != self._table_sig:
-            self._build_table(entries)
-            self._table_sig = sig
+    @property
+    def _table(self):
+        """The table on the device (None before the first update)."""
+        return self._dev.rows
 
     def update_weights(self):
-        entries = self._entries()
-        self._ensure_table(entries)
-        self._launch(self._table.data_ptr(), len(entries), self._total_blocks, stream_handle())
+        t = self._dev
+        t.ensure(self._entries())
+        self._launch(t.ptr, t.ntens, t.blocks, stream_handle())
 
     # -- the state file -----------------------------------------------------------------------
 

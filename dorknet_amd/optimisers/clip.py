@@ -10,51 +10,43 @@ optimiser applies (``optimiser.learnable_layers``), as three launches and no hos
 
 The norm is bit-identical from run to run, and across ranks that hold the same gradients.  The
 table (one 24-byte row ``{g, n, first_block}`` per gradient tensor), the workspace and the two
-output words are cached on the optimiser and rebuilt only when a pointer or a size changes.
+output words are cached on the optimiser (``_clip_state``); the table (dorknet_amd/_table.py) and the
+workspace are rebuilt only when a pointer or a size changes.
 ``Adam(max_grad_norm=c)`` uses the norm launches alone and reads ``out[1]`` in its update.
 """
 from __future__ import annotations
 
 import math
 
-import numpy as np
 import torch
 
 from .._hip import lib, stream_handle
+from .._table import DeviceTable
 
-CHUNK = 2048  # elements per block of the norm and scale kernels (kGradChunk, csrc/adam.hip)
+CHUNK = 2048  # elements per block of the norm and scale kernels (kChunk, csrc/multi_tensor.hip)
 
 
 class _ClipState:
-    __slots__ = ("sig", "table", "ntens", "blocks", "ws", "out", "checked_under")
+    """The table, the workspace sized for it and the two output words."""
+
+    def __init__(self):
+        self.table = DeviceTable(CHUNK, "clip_grad_norm", ("grads", "grad"), 1, hint="call it after network.to_gpu()")
+        self.ws = self.out = None
+        self.checked_under = None  # Adam: the signature of its own table this one was last checked under
 
 
 def _state(optimiser):
-    grads = [layer.grads[k] for layer in optimiser.learnable_layers for k in layer.learned_params.keys()]
-    try:
-        sig = tuple((g.data_ptr(), g.numel()) for g in grads)
-    except AttributeError:  # host arrays: the check below says what is wrong
-        sig = None
     st = getattr(optimiser, "_clip_state", None)
-    if st is not None and sig is not None and st.sig == sig:
-        return st
-    rows, block0 = [], 0
-    for g in grads:
-        if not (isinstance(g, torch.Tensor) and g.is_cuda and g.dtype == torch.float32 and g.is_contiguous()):
-            raise RuntimeError("clip_grad_norm: grads must be contiguous fp32 device tensors (call it after "
-                               "network.to_gpu())")
-        rows.append((g.data_ptr(), g.numel(), block0))
-        block0 += -(-g.numel() // CHUNK)
-    new = _ClipState()
-    new.sig = sig
-    new.checked_under = None  # Adam: the signature of its own table this one was last checked under
-    new.table = torch.as_tensor(np.array(rows, dtype=np.int64).reshape(-1, 3), device="cuda")
-    new.ntens = len(rows)
-    new.blocks = block0
-    new.ws = torch.empty(max(int(lib.dk_grad_norm_workspace_bytes(block0)), 8), dtype=torch.uint8, device="cuda")
-    new.out = st.out if st is not None else torch.zeros(2, dtype=torch.float32, device="cuda")
-    optimiser._clip_state = new
-    return new
+    if st is None:
+        st = optimiser._clip_state = _ClipState()
+    t = st.table
+    if t.ensure([(layer.grads[k],) for layer in optimiser.learnable_layers for k in layer.learned_params.keys()]):
+        st.checked_under = None
+        st.ws = torch.empty(max(int(lib.dk_grad_norm_workspace_bytes(t.blocks)), 8), dtype=torch.uint8,
+                            device="cuda")
+        if st.out is None:
+            st.out = torch.zeros(2, dtype=torch.float32, device="cuda")
+    return st
 
 
 def measure_grad_norm(optimiser, max_norm=None, unchanged=False):
@@ -66,8 +58,9 @@ def measure_grad_norm(optimiser, max_norm=None, unchanged=False):
     if st is None:
         st = _state(optimiser)
     c = 0.0 if max_norm is None or not math.isfinite(max_norm) else float(max_norm)
-    lib.dk_grad_norm_multi_f32(st.table.data_ptr(), st.ntens, st.blocks, c, st.out.data_ptr(), st.ws.data_ptr(),
-                               st.ws.numel(), stream_handle())
+    t = st.table
+    lib.dk_grad_norm_multi_f32(t.ptr, t.ntens, t.blocks, c, st.out.data_ptr(), st.ws.data_ptr(), st.ws.numel(),
+                               stream_handle())
     return st.out
 
 
@@ -80,6 +73,6 @@ def clip_grad_norm(optimiser, max_norm):
     Under ``parallel.DataParallel`` call it after ``finish()``: the norm is then of the averaged
     gradients and bit-identical on every rank, so every rank applies the same scale."""
     out = measure_grad_norm(optimiser, max_norm)
-    st = optimiser._clip_state
-    lib.dk_grad_scale_multi_f32(st.table.data_ptr(), st.ntens, st.blocks, out.data_ptr() + 4, stream_handle())
+    t = optimiser._clip_state.table
+    lib.dk_grad_scale_multi_f32(t.ptr, t.ntens, t.blocks, out.data_ptr() + 4, stream_handle())
     return out[0]

@@ -638,8 +638,9 @@ int dk_softmax_xent_bwd_f32(const float* p, const float* y_onehot, int B, int K,
  *     dk_rmsprop_multi_f32:  c = decay * c + one_minus_decay * (g * g);
  *                            d = ((-lr) * g) / sqrt(c + eps);  w = w + d;  c stored back
  *   (the reference's eps is 1e-5; one_minus_decay is 1 - decay formed in double by the caller).
- *   Both return DK_ERR_ARGS for a NULL table with ntens > 0 or a negative count.
- *   Adam / AdamW (dorknet_amd/csrc/adam.hip; no optimiser of the reference: torch.optim.Adam / AdamW,
+ *   All three return DK_ERR_ARGS for a NULL table with ntens > 0, a negative count or total_blocks
+ *   above 2^31 - 1, and 0 for ntens == 0.  (Every table entry point is in dorknet_amd/csrc/multi_tensor.hip.)
+ *   Adam / AdamW (no optimiser of the reference: torch.optim.Adam / AdamW,
  *   non-amsgrad, as single fp32 operations) has a table of its own, 56 bytes per entry:
  *   { float* w; const float* g; float* m; float* v; int64 n; int64 first_block; int64 flags },
  *   256 elements per block, flags bit 0 = apply keep (decoupled weight decay).  The caller forms in
@@ -660,7 +661,11 @@ int dk_softmax_xent_bwd_f32(const float* p, const float* y_onehot, int B, int K,
  *                            (torch's clip_grad_norm_); max_norm <= 0 or infinite: out[1] = 1.
  *                            ws: dk_grad_norm_workspace_bytes(total_blocks), else DK_ERR_WORKSPACE.
  *     dk_grad_scale_multi_f32: g = scale[0] * g in place, one rounding; a scale of 1 writes nothing.
- *   l2 loss term: regularisers/l2.py:12-14; scale: l2.py:16-17 and DP averaging.
+ *   l2 loss term: regularisers/l2.py:12-14; scale: l2.py:16-17 and DP averaging.  dk_l2_loss_multi_f32 adds
+ *   all of a network's terms in two launches: out[0] = add_to[0] (may be NULL) + sum_t 0.5 * strength_t *
+ *   sum(w_t^2) over table entries { const float* w; int64 n; int64 first_block; float strength; float pad }
+ *   (32 bytes), first_block = sum of ceil(n / 2048) over the preceding entries; ntens or total_blocks <= 0:
+ *   DK_ERR_ARGS; ws: dk_l2_multi_workspace_bytes(total_blocks), else DK_ERR_WORKSPACE.
  *   colsum: bias gradients, np.sum(upstream_dx, axis=(0,2,3)) (convolution.py:91-92 etc.).
  * ------------------------------------------------------------------------------------- */
 int dk_sgd_momentum_multi_f32(const void* table, int ntens, long long total_blocks, float lr, float momentum, float grad_scale, void* stream);

@@ -6,8 +6,9 @@ update).  HIP events around --calls back-to-back update_weights() after a warm-u
 the optimisers taking turns within a repeat; per call: the median over the repeats and their
 min-max.  Then the same for the C entries alone on the tables update_weights() built (no Python walk
 over the tensors): back-to-back update_weights() calls are paced by the host, the entries alone by
-the launches.  All share the network's parameters and gradients; the gradients are small, so the
-weights stay finite.
+the launches; that section has one more row, the l2 term of the forward pass (the two launches of
+dk_l2_loss_multi_f32 over the network's l2-regularised weights).  All share the network's parameters
+and gradients; the gradients are small, so the weights stay finite.
     python scripts/optimiser_bench.py [--calls 100] [--repeats 5]
 """
 import argparse
@@ -19,7 +20,7 @@ sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import numpy as np  # noqa: E402
 import torch  # noqa: E402
 
-from dorknet_amd._hip import stream_handle  # noqa: E402
+from dorknet_amd._hip import lib, stream_handle, workspace  # noqa: E402
 from dorknet_amd.optimisers.Adam import Adam  # noqa: E402
 from dorknet_amd.optimisers.clip import measure_grad_norm  # noqa: E402
 from dorknet_amd.optimisers.RMSProp import RMSProp  # noqa: E402
@@ -48,17 +49,28 @@ def main():
     nparam = sum(v.numel() for l in layers for v in l.learned_params.values())
     st = stream_handle()
 
-    def entry_only(opt):  # the C entries on the tables update_weights built: the launches without the Python walk
-        if getattr(opt, "max_grad_norm", None) is not None:
-            out = measure_grad_norm(opt, opt.max_grad_norm, unchanged=True)  # the cached table: no walk either
-            opt._launch(opt._table.data_ptr(), ntens, opt._total_blocks, st, out.data_ptr() + 4)
-        else:
-            opt._launch(opt._table.data_ptr(), ntens, opt._total_blocks, st)
+    # the l2 term of a training forward pass (dk_l2_loss_multi_f32 over the network's l2-regularised
+    # weights), on the table the network builds for it
+    loss = torch.zeros((), dtype=torch.float32, device="cuda")
+    l2_out = net._l2_total(net._l2_plan(), loss)
+    l2 = net._l2_table
+    l2_nb = lib.dk_l2_multi_workspace_bytes(l2.blocks)
+    l2_ws = workspace.get(l2_nb)
 
-    for what, call in (("update_weights()", lambda opt: opt.update_weights()), ("the C entries alone", entry_only)):
-        times = {name: [] for name, _ in opts}
+    def entry_only(opt):  # the C entries on the tables update_weights built: the launches without the Python walk
+        if opt is None:
+            lib.dk_l2_loss_multi_f32(l2.ptr, l2.ntens, l2.blocks, loss.data_ptr(), l2_out.data_ptr(), l2_ws, l2_nb, st)
+        elif getattr(opt, "max_grad_norm", None) is not None:
+            out = measure_grad_norm(opt, opt.max_grad_norm, unchanged=True)  # the cached table: no walk either
+            opt._launch(opt._dev.ptr, ntens, opt._dev.blocks, st, out.data_ptr() + 4)
+        else:
+            opt._launch(opt._dev.ptr, ntens, opt._dev.blocks, st)
+
+    for what, call, rows in (("update_weights()", lambda opt: opt.update_weights(), opts),
+                             ("the C entries alone", entry_only, opts + [("l2 term", None)])):
+        times = {name: [] for name, _ in rows}
         for r in range(a.repeats + 1):  # repeat 0 is the warm-up (and builds the tables)
-            for name, opt in opts:
+            for name, opt in rows:
                 e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
                 e0.record()
                 for _ in range(a.calls):
@@ -69,7 +81,7 @@ def main():
                     times[name].append(1e3 * e0.elapsed_time(e1) / a.calls)
         print("{} tensors, {} parameters; us per call of {} over {} back-to-back calls, {} repeats".format(
             ntens, nparam, what, a.calls, a.repeats))
-        for name, _ in opts:
+        for name, _ in rows:
             t = sorted(times[name])
             print("  {:12s} median {:7.2f}  min {:7.2f}  max {:7.2f}".format(name, t[len(t) // 2], t[0], t[-1]))
 

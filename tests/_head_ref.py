@@ -22,20 +22,23 @@ Global average pooling, x[N][HW][C] (elementwise.hip:176-193 gap_fwd_kernel; :23
               outer ReLU 1-Lipschitz: ej.  out: u (HW + 1) sum y / HW + (1 + u HW) sum ej / HW.  The mask byte is the
               reference decision: join_margin = min |va + vb| / (2 ej) must exceed 1 (asserted on the host).
 
-Column sums, in[M][N] (elementwise.hip:555-579, :627-632, :864-875): every term widened to fp64 (:567, :569), added in
-fp64 within a chunk of rpc = ceil(M / chunks) rows, chunks = min(ceil(M / 64), 512), the chunk sums added in fp64 (:577)
-and cast once (:578).  M + chunks additions in any grouping, one fp32 rounding:
+Column sums, in[M][N] (elementwise.hip: colsum_partial_kernel, colsum_final_kernel, colsum_chunks, dk_colsum_f32 /
+dk_colsum_bf16): every term widened to fp64 (both loops of colsum_partial_kernel), added in fp64 within a chunk of
+rpc = ceil(M / chunks) rows, chunks = min(ceil(M / 64), 512), the chunk sums added in fp64 and cast once
+(colsum_final_kernel).  M + chunks additions in any grouping, one fp32 rounding:
                                                      u |ref| + (1 + u) e (M + chunks) sum|x|.
     The ill-conditioned column (column 0 of every case with M >= 7) holds large cancelling values whose sum is of the
     order of one term's last bits: there sum|x| / |ref| is above 10^6 and fp32 accumulation (u per addition) is far
     outside the bound while fp64 accumulation is inside.
 
-l2 term (elementwise.hip:479-497 l2_loss_kernel; :511-551 the multi-tensor pair): v * v of a widened fp32 is exact in
-fp64 (48 bits); n terms over 256 strided threads and a 256-leaf tree (:483-492), 0.5 * (double) strength exact, one
-fp64 product, one cast (:494):                        ev = u |v| + (1 + u) e (n + 258) |v|   (all terms positive).
-    accumulate: out[0] + v in fp32 (:495): + u (|prior + v| + ev).
-    multi: per 2048-element chunk the same sum (:519-534), the chunk values added in fp64 over 256 strided threads and
-    a tree with add_to widened (:543-550), one cast:  u |ref| + (1 + u) e (n_total + parts + 258) (|add_to| + sum v_t).
+l2 term (l2_loss_kernel in elementwise.hip; l2_multi_partial_kernel and l2_multi_final_kernel in multi_tensor.hip):
+v * v of a widened fp32 is exact in fp64 (48 bits); n terms over 256 strided threads and a 256-leaf tree (block_sum,
+dk_common.h), 0.5 * (double) strength exact, one fp64 product, one cast:
+                                                     ev = u |v| + (1 + u) e (n + 258) |v|   (all terms positive).
+    accumulate: out[0] + v in fp32: + u (|prior + v| + ev).
+    multi: per 2048-element chunk the same sum (chunk_sum_squares), the chunk values added in fp64 over 256 strided
+    threads and a tree (sum_partials) with add_to widened, one cast:
+                                                     u |ref| + (1 + u) e (n_total + parts + 258) (|add_to| + sum v_t).
 
 Softmax with cross-entropy, x[B][K] (elementwise.hip:262-375).  No max shift (losses.py:15-16), in the reference
 neither.  Every term is positive, so the bounds on P are relative to p:
@@ -67,7 +70,8 @@ Dense layer (gemm_dense.hip:7-47 on gemm_engine.h), the forms of tests/_conv_ref
     16-byte pointer, else the scalar loaders; ep_store (:1427-1430): OUT % 4 == 0, 16-byte output and bias, else the
     scalar store.
 
-Exact kernels (elementwise.hip:13-92, :56-59, :581-625, :921-954): bitwise references.  relu: v > 0 ? v : 0, mask v > 0
+Exact kernels (elementwise.hip: relu_fwd_kernel, relu_bwd_kernel, mask_to_f32_kernel, add_kernel, the nchw_to_nhwc and
+nhwc_unpad kernels, scale_kernel, the two cast kernels): bitwise references.  relu: v > 0 ? v : 0, mask v > 0
 (-0.0 -> +0.0, NaN -> 0 with mask 0); add, scale: one IEEE operation in numpy fp32, subnormal operands and results
 included (no build flag flushes them; on the host under tests/_optim_twin.ieee_host, since loading the oracle's
 -ffast-math library leaves the thread flushing them); casts: torch-CPU round-to-nearest-even / exact widening; layout
@@ -90,7 +94,7 @@ EXPF = 2 * U        # ASSUMPTION (module docstring): one ulp; not fitted
 LOGF = 2 * U        # ASSUMPTION (module docstring): one ulp; not fitted
 L2 = float(f32(1e-3))               # = _conv_ref.L2
 MAX_ELEMENTS = 1 << 20              # cap on the elements of any one tensor of a case, GRID_STRIDE_N alone excepted
-GRID_STRIDE_N = 16384 * 1024 + 1029     # grid4's cap (elementwise.hip:640-645) is 16384 blocks x 256 threads x 4:
+GRID_STRIDE_N = 16384 * 1024 + 1029     # grid4's cap (elementwise.hip) is 16384 blocks x 256 threads x 4:
 #                                         257 float4 chunks take a second trip, and the tail is 1029 % 4 = 1 element
 
 
@@ -245,10 +249,12 @@ L2_PRIOR = 3.25                             # the value accumulate = 1 adds onto
 L2_CHUNK = 2048
 # multi-tensor tables: (sizes, strengths).  "t1": a chunk of one element, one short of / exactly / one past a chunk,
 # two whole chunks and a tail; one strength 0.  "t2": 256 * 2048 + 1 elements = 257 chunks, so that with the others
-# the final kernel's strided loop (256 threads) takes a second trip.
+# the final kernel's strided loop (256 threads) takes a second trip.  "t3": 1025 tensors of 3 elements, one more than
+# the first-block entries the owner search keeps in LDS: its linear scan over the table in memory.
 L2_TABLES = {
     "t1": ((1, 2047, 2048, 2049, 5000), (1e-3, 5e-4, 0.0, 2e-3, 1e-2)),
     "t2": ((300, 256 * 2048 + 1, 2049), (1e-3, 1e-4, 5e-3)),
+    "t3": ((3,) * 1025, tuple(1e-4 * (k + 1) for k in range(1025))),
 }
 L2_ADD_TO = 1.7
 

@@ -1,11 +1,12 @@
-"""numpy twins of the reference's SGD and RMSProp updates for one tensor, written as the reference
-writes them (optimisers/SGD.py:20-24, optimisers/RMSProp.py:28-36): np.float32 arrays meet
+"""numpy twins of the reference's SGD, SGD-momentum and RMSProp updates for one tensor, written as the
+reference writes them (optimisers/SGD.py:20-24, SGDMomentum.py:33-39, RMSProp.py:28-36): np.float32 arrays meet
 Python-float scalars, so every array operation is one correctly rounded fp32 operation and each
 scalar is rounded to fp32 once, where it meets the array.  ``1 - decay`` is formed in Python
 double; the square is ``g * g`` (np.power(g, 2) is the same product); 1e-5 is a Python float.
 The fp64 versions are the same expressions over float64 arrays.
 
-(oracle/ref.py holds the SGD-momentum twin; the oracle is frozen, so these live here.)
+(oracle/ref.py holds the oracle's own sgd_momentum_update, without the gradient scale or the fp32 and
+denormal guards; the oracle is frozen, so these live here.)
 """
 import contextlib
 import ctypes
@@ -55,6 +56,18 @@ def sgd_update(W, g, lr):
     with ieee_host():
         dx = -lr * g
         return W + dx
+
+
+def sgd_momentum_update(W, g, v, lr, mom, gscale=1.0):
+    """SGDMomentum.update_weights (optimisers/SGDMomentum.py:33-39) for one tensor, after the gradient
+    scale of dk_sgd_momentum_multi_f32 (applied unless it is exactly 1); returns (W, v)."""
+    _f32(W, g, v)
+    lr, mom, gscale = float(lr), float(mom), float(gscale)
+    with ieee_host(), np.errstate(under="ignore"):
+        if gscale != 1.0:
+            g = gscale * g
+        dx = -lr * g + mom * v
+        return W + dx, dx
 
 
 def rmsprop_update(W, g, c, lr, decay):

@@ -271,6 +271,36 @@ def test_scale():
         assert same_bits(host(g), twin.scale_update(a, 0.3)) and not same_bits(host(g), a)
 
 
+def test_norm_and_scale_past_the_lds_table():
+    """1025 gradient tensors, 3 elements each (the owner search's linear fallback over 24-byte rows): what
+    test_norm and test_scale assert."""
+    rng = np.random.default_rng(26)
+    T, n = 1025, 3
+    G = rng.standard_normal(T * n).astype(np.float32)
+    G[:2] = 1e-30  # their fp32 squares vanish
+    bg, (g,), mask = _carve([G])
+    tab, blocks = grad_table([g[i * n:(i + 1) * n] for i in range(T)])
+    assert blocks == T
+    want = twin.norm_f64([G])
+    c = 0.25 * want
+    out = torch.full((2,), 7.0, dtype=torch.float32, device="cuda")
+    o = _norm_call(tab, T, blocks, c, out)
+    assert abs(float(o[0]) - want) <= np.spacing(np.float32(want)), (o[0], want)
+    assert same_bits(o[1:], [twin.clip_scale(o[0], c)]) and 0.2 < o[1] < 0.3
+    assert same_bits(o, _norm_call(tab, T, blocks, c, torch.zeros_like(out)))  # bit-identical from run to run
+    o3 = _norm_call(tab, T, blocks, 0.0, out)  # measure only
+    assert same_bits(o3[:1], o[:1]) and o3[1] == 1
+    assert same_bits(host(g), G)  # the norm reads only
+    one, s = dev([1.0]), dev([0.3])
+    lib.dk_grad_scale_multi_f32(tab.data_ptr(), T, blocks, one.data_ptr(), stream_handle())
+    torch.cuda.synchronize()
+    assert same_bits(host(g), G)  # a scale of 1 changes no bit
+    lib.dk_grad_scale_multi_f32(tab.data_ptr(), T, blocks, s.data_ptr(), stream_handle())
+    torch.cuda.synchronize()
+    assert _guards_intact(bg, mask)
+    assert same_bits(host(g), twin.scale_update(G, 0.3)) and not same_bits(host(g), G)
+
+
 # ---- through the layers ----------------------------------------------------------------------------
 
 def _net(seed=20):
@@ -414,8 +444,9 @@ def test_clip_grad_norm_through_the_layers(cls):
     assert abs(float(norm) - want) <= np.spacing(np.float32(want))
     assert all(same_bits(host(l.grads[k]), G[(l.layer_name, k)]) for l in opt.learnable_layers for k in l.grads)
     st = opt._clip_state
+    tab, ws = st.table.rows, st.ws
     norm = clip.clip_grad_norm(opt, 0.5 * want)
-    assert opt._clip_state is st  # the table and the workspace are reused
+    assert opt._clip_state is st and st.table.rows is tab and st.ws is ws  # the table and the workspace are reused
     s = twin.clip_scale(host(norm), 0.5 * want)
     assert 0.4 < s < 0.6 and same_bits(host(st.out)[1:], [s])
     for l in opt.learnable_layers:
@@ -425,7 +456,7 @@ def test_clip_grad_norm_through_the_layers(cls):
     dense = net.layers[-1]
     dense.grads["weights"] = dense.grads["weights"].clone()
     clip.clip_grad_norm(opt, 0.0)
-    assert opt._clip_state is not st
+    assert opt._clip_state.table.rows is not tab
 
 
 @pytest.mark.parametrize("wd", [0.0, 0.01], ids=["Adam", "AdamW"])

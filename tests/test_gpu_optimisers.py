@@ -1,7 +1,8 @@
-"""SGD and RMSProp on the GPU (dk_sgd_multi_f32, dk_rmsprop_multi_f32; dorknet_amd/optimisers) against
-the numpy twins of the reference's expressions (tests/_optim_twin.py), bit for bit: every operation of
-an update is one correctly rounded fp32 operation and nothing is reduced, so there is no freedom of
-order and no tolerance.  A difference means a contracted, reassociated or approximate operation.
+"""SGD, SGD momentum and RMSProp on the GPU (dk_sgd_multi_f32, dk_sgd_momentum_multi_f32,
+dk_rmsprop_multi_f32; dorknet_amd/optimisers) against the numpy twins of the reference's expressions
+(tests/_optim_twin.py), bit for bit: every operation of an update is one correctly rounded fp32
+operation and nothing is reduced, so there is no freedom of order and no tolerance.  A difference
+means a contracted, reassociated or approximate operation.
 Also: the optimiser state file (save_state_to_h5 / load_state_from_h5) through a training run."""
 import numpy as np
 import pytest
@@ -139,6 +140,68 @@ def test_more_tensors_than_the_lds_table_holds():
     assert same_bits(host(wr), Wr) and same_bits(host(cr), Cr)
 
 
+def momentum_call(tab, ntens, blocks, gscale, lr=LR, mom=DECAY):
+    lib.dk_sgd_momentum_multi_f32(tab.data_ptr(), ntens, blocks, float(lr), float(mom), float(gscale),
+                                  stream_handle())
+
+
+@pytest.mark.parametrize("gscale", [1.0, 0.5], ids=["plain", "grad_scale"])
+def test_momentum_raw_entry_bit_for_bit(gscale):
+    """dk_sgd_momentum_multi_f32 against its twin: g' = gscale * g (not at gscale = 1), d = (-lr) * g' +
+    mom * v, w = w + d, v = d, one rounding per operation, nothing reduced: no tolerance.  Planted into
+    the 4099-element tensor, on a velocity of 0: PLANTED's gradients (g = 0: the weight must not move;
+    g = +-1e-20) and g = 1e-37 at index 7, whose product with lr is a denormal that must survive in v."""
+    rng = np.random.default_rng(14)
+    W = [rng.standard_normal(n).astype(np.float32) for n in SIZES]
+    V = [rng.standard_normal(n).astype(np.float32) for n in SIZES]
+    V[0][:] = 0  # a fresh velocity
+    for i in (0, 5, 7, 300, 4096):
+        V[-1][i] = 0
+    ws, vs = [dev(w) for w in W], [dev(v) for v in V]
+    gs = [torch.empty(n, dtype=torch.float32, device="cuda") for n in SIZES]
+    tab, blocks = table(ws, gs, vs)
+    W_first = [w.copy() for w in W]
+    W_before = W_first[-1]
+    for step in range(3):  # consecutive steps: the velocity carries over
+        G = _inputs(rng, step)
+        G[-1][7] = 1e-37
+        for g, a in zip(gs, G):
+            g.copy_(dev(a))
+        momentum_call(tab, len(SIZES), blocks, gscale)
+        torch.cuda.synchronize()
+        for t, n in enumerate(SIZES):
+            W[t], V[t] = twin.sgd_momentum_update(W[t], G[t], V[t], LR, DECAY, gscale)
+            assert same_bits(host(vs[t]), V[t]), ("v", step, n)
+            assert same_bits(host(ws[t]), W[t]), ("w", step, n)
+            assert same_bits(host(gs[t]), G[t]), ("gradients are read only", step, n)
+        w, v = host(ws[-1]), host(vs[-1])
+        for i in (0, 4096):  # g = 0 on v = 0: nothing moves
+            assert same_bits(w[i:i + 1], W_before[i:i + 1]) and v[i] == 0, (step, i)
+        for i in (5, 300):  # the tiny step is kept in the velocity
+            assert v[i] != 0 and abs(v[i]) < 1e-21, (step, i)
+        # a denormal survived: not flushed (as bits: the host may compare denormals as zero)
+        assert 0 < int(v.view(np.uint32)[7] & 0x7fffffff) < 0x00800000, step
+    assert all(not same_bits(host(w), a) for w, a in zip(ws, W_first))  # and ordinary elements moved
+
+
+def test_momentum_past_the_lds_table():
+    """1025 tensors, 3 elements each: the owner search's linear fallback in the momentum kernel."""
+    rng = np.random.default_rng(15)
+    T, n = 1025, 3
+    W = rng.standard_normal(T * n).astype(np.float32)
+    G = rng.standard_normal(T * n).astype(np.float32)
+    V = rng.standard_normal(T * n).astype(np.float32)
+    w, g, v = dev(W), dev(G), dev(V)
+    cut = lambda t: [t[i * n:(i + 1) * n] for i in range(T)]  # noqa: E731
+    tab, blocks = table(cut(w), cut(g), cut(v))
+    assert blocks == T
+    momentum_call(tab, T, blocks, 0.5)
+    torch.cuda.synchronize()
+    W2, V2 = twin.sgd_momentum_update(W, G, V, LR, DECAY, 0.5)
+    assert same_bits(host(w), W2) and same_bits(host(v), V2) and same_bits(host(g), G)
+    assert not same_bits(W2, W)
+
+
 def test_no_stray_writes():
     """Every w and c is carved out of a larger buffer between NaN guard words; the guards (and the
     gradients) are untouched."""
@@ -181,6 +244,48 @@ def test_no_stray_writes():
         Wr, Cr = twin.rmsprop_update(W[t], G[t], C[t], LR, DECAY)
         assert same_bits(host(ws[t]), twin.sgd_update(W[t], G[t], LR))
         assert same_bits(host(wr[t]), Wr) and same_bits(host(cr[t]), Cr)
+
+
+# ---- the table builder on the device ---------------------------------------------------------------
+
+def test_device_table_rebuilds_only_on_change():
+    """DeviceTable.ensure: the rows are this file's own statement of the layout; a second call with the
+    same tensors keeps the device tensor and the signature object; a replaced pointer, a changed size or
+    a flipped extra word (Adam's decay flag) rebuilds; sizes that disagree are refused."""
+    from dorknet_amd._table import DeviceTable
+    new = lambda n: torch.zeros(n, dtype=torch.float32, device="cuda")  # noqa: E731
+    ws, gs, cs = [new(n) for n in SIZES], [new(n) for n in SIZES], [new(n) for n in SIZES]
+    t = DeviceTable(256, "RMSProp", ("parameters, grads and caches", "grad / cache"), 3)
+    assert t.ensure(list(zip(ws, gs, cs))) is True
+    want, blocks = table(ws, gs, cs)
+    assert torch.equal(t.rows, want) and (t.ntens, t.blocks) == (len(SIZES), blocks) and t.ptr == t.rows.data_ptr()
+    rows, sig = t.rows, t.sig
+    assert t.ensure(list(zip(ws, gs, cs))) is False and t.rows is rows and t.sig is sig
+    cs[2] = cs[2].clone()  # a pointer
+    assert t.ensure(list(zip(ws, gs, cs))) is True and t.rows is not rows and t.sig is not sig
+    assert torch.equal(t.rows, table(ws, gs, cs)[0])
+    ws[0], gs[0], cs[0] = new(300), new(300), new(300)  # a size: every later first_block moves
+    assert t.ensure(list(zip(ws, gs, cs))) is True and torch.equal(t.rows, table(ws, gs, cs)[0])
+    assert t.blocks == blocks + 1
+    rows = t.rows
+    gs[1] = new(SIZES[1] + 1)
+    with pytest.raises(ValueError, match="^RMSProp: grad / cache size mismatch$"):
+        t.ensure(list(zip(ws, gs, cs)))
+    assert t.rows is rows  # a refused call leaves the table as it was
+    # no state (plain SGD): 0 pointers
+    s = DeviceTable(256, "SGD", ("parameters and grads", "grad"), 3)
+    s.ensure([(w, g, None) for w, g in zip(ws, cs)])
+    assert torch.equal(s.rows, table(ws, cs)[0])
+    # an extra word per row
+    a = DeviceTable(256, "Adam", ("parameters, grads and moments", "grad / moment"), 4)
+    ms = [new(n) for n in (300, *SIZES[1:])]
+    assert a.ensure([(w, c, m, c, 1) for w, c, m in zip(ws, cs, ms)]) is True
+    assert a.rows.shape == (len(SIZES), 7) and a.rows[:, 6].tolist() == [1] * len(SIZES)
+    assert a.rows[:, 5].tolist() == t.rows[:, 4].tolist() and a.rows[:, 2].tolist() == [m.data_ptr() for m in ms]
+    rows = a.rows
+    assert a.ensure([(w, c, m, c, 1) for w, c, m in zip(ws, cs, ms)]) is False and a.rows is rows
+    assert a.ensure([(w, c, m, c, i & 1) for i, (w, c, m) in enumerate(zip(ws, cs, ms))]) is True
+    assert a.rows is not rows and a.rows[:, 6].tolist() == [i & 1 for i in range(len(SIZES))]
 
 
 # ---- through the layers ----------------------------------------------------------------------------

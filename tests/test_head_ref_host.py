@@ -236,7 +236,7 @@ def test_gap_join_honest_and_margin(name, variant):
 
 
 # ---------------------------------------------------------------------------------------------------------
-# column sums and l2 (elementwise.hip:479-579)
+# column sums and l2 (elementwise.hip: the colsum kernels, l2_loss_kernel; multi_tensor.hip: the l2 multi pair)
 # ---------------------------------------------------------------------------------------------------------
 
 def h_colsum(x, grouping, defect=None):

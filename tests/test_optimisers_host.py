@@ -196,6 +196,20 @@ def test_argument_errors_without_a_device():
     assert lib.dk_abi_version() == 1
 
 
+@pytest.mark.skipif(not os.path.exists(_hip.LIB_PATH), reason="run __graft_entry__.build() first")
+def test_momentum_argument_errors_without_a_device():
+    """dk_sgd_momentum_multi_f32 refuses what its siblings refuse, before any launch."""
+    import ctypes
+    lib = _hip.lib
+    buf = ctypes.create_string_buffer(64)
+    p = ctypes.addressof(buf)
+    for table, ntens, blocks in [(None, 1, 1), (p, -1, 1), (p, 1, -1), (p, 1, 1 << 31)]:
+        with pytest.raises(_hip.HipError, match="bad arguments"):
+            lib.dk_sgd_momentum_multi_f32(table, ntens, blocks, 0.1, 0.9, 1.0, None)
+    assert lib.dk_sgd_momentum_multi_f32(None, 0, 0, 0.1, 0.9, 1.0, None) == 0  # nothing to do
+    assert lib.dk_sgd_momentum_multi_f32(p, 0, 5, 0.1, 0.9, 1.0, None) == 0
+
+
 # ---- the state file ------------------------------------------------------------------------------
 
 def _small_net():

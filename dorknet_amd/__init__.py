@@ -20,7 +20,7 @@ _ALIASES = [
     "layers.residual_block", "layers.pooling", "layers.reshape", "layers.dropout", "layers.losses",
     "network", "network.feed_forward_network",
     "optimisers", "optimisers.SGDMomentum", "optimisers.SGD", "optimisers.RMSProp",
-    "optimisers.Adam", "optimisers.clip",
+    "optimisers.Adam", "optimisers.LARS", "optimisers.clip",
     "regularisers", "regularisers.l2",
 ]
 

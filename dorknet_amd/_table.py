@@ -1,9 +1,10 @@
 """The device table of the multi-tensor kernels (dorknet_amd/csrc/multi_tensor.hip): one int64 row
 ``{pointers..., n, first_block, extra words...}`` per tensor, ``first_block`` the running sum of
-``ceil(n / per_block)``.  The four layouts of include/dorknet_hip.h are this one shape:
+``ceil(n / per_block)``.  The five layouts of include/dorknet_hip.h are this one shape:
 
     SGD, SGDMomentum, RMSProp   {w, g, state, n, first_block}              256 elements per block
     Adam                        {w, g, m, v, n, first_block, flags}        256
+    LARS                        {w, g, v, n, first_block, flags}           2048 (flags bit 0: adapt)
     the gradient norm / scale   {g, n, first_block}                        2048
     the l2 term                 {w, n, first_block, strength as fp32}      2048
 

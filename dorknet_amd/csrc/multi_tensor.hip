@@ -1,11 +1,11 @@
 // Every kernel that walks a table of tensors in one launch, gfx950: the optimiser updates (SGD, SGD
-// momentum, RMSProp, Adam / AdamW), the global gradient norm with its scale, and the l2 loss term of a
-// whole network.  The host builds the tables in dorknet_amd/_table.py; the row layouts are part of the
-// ABI (include/dorknet_hip.h).  DESIGN.md sections 12 and 21.
+// momentum, RMSProp, Adam / AdamW, LARS), the global gradient norm with its scale, the per-tensor norms
+// and trust ratios of LARS, and the l2 loss term of a whole network.  The host builds the tables in dorknet_amd/_table.py; the row layouts are part of the
+// ABI (include/dorknet_hip.h).  DESIGN.md sections 12, 21 and 22.
 //
 // A table row is {pointers..., n, first_block, extra words...}; block b of the launch belongs to the
-// last row with first_block <= b (owner_entry) and works on one chunk of that tensor: 256 elements
-// in the updates, 2048 in the reductions and the scale.
+// last row with first_block <= b (owner_index / owner_entry) and works on one chunk of that tensor:
+// 256 elements in the updates, 2048 in the reductions, the scale and all three LARS kernels.
 //
 // The updates are written as single fp32 operations, each rounded once and never fused (mul_1r /
 // add_1r, sqrtf, __fdiv_rn), denormals kept, so they are bit-identical to their numpy twins.  The
@@ -34,6 +34,15 @@ struct AdamEntry {  // 56 bytes
   long long flags;  // bit 0: apply keep (decoupled weight decay)
 };
 
+struct LarsEntry {  // 48 bytes
+  float* w;
+  const float* g;
+  float* v;  // the velocity
+  long long n;
+  long long block0;
+  long long flags;  // bit 0: adapt (scale the step by the tensor's trust ratio, add weight_decay * w)
+};
+
 struct GradEntry {  // 24 bytes
   float* g;
   long long n;
@@ -51,12 +60,12 @@ struct L2Entry {  // 32 bytes
 constexpr int kOwnerLds = 1024;
 constexpr int kChunk = 2048;  // elements per block of the norm, scale and l2 kernels
 
-// The table entry owning this block (the last one with block0 <= blockIdx.x): the block0 column is
-// loaded into LDS in parallel (one load latency) and searched there by bisection; a linear scan of
-// the global table (~100 dependent loads for the last blocks of a network's table) past kOwnerLds
-// entries.  Called by all 256 threads of the block (it holds barriers).
+// The index of the table entry owning this block (the last one with block0 <= blockIdx.x): the block0
+// column is loaded into LDS in parallel (one load latency) and searched there by bisection; a linear
+// scan of the global table (~100 dependent loads for the last blocks of a network's table) past
+// kOwnerLds entries.  Called by all 256 threads of the block (it holds barriers).
 template <class Entry>
-__device__ __forceinline__ Entry owner_entry(const Entry* __restrict__ tab, int ntens) {
+__device__ __forceinline__ int owner_index(const Entry* __restrict__ tab, int ntens) {
   __shared__ long long b0s[kOwnerLds];
   __shared__ int owner;
   const long long b = blockIdx.x;
@@ -77,7 +86,13 @@ __device__ __forceinline__ Entry owner_entry(const Entry* __restrict__ tab, int 
   } else {
     while (t + 1 < ntens && tab[t + 1].block0 <= b) ++t;
   }
-  return tab[t];
+  return t;
+}
+
+// The owning entry itself.
+template <class Entry>
+__device__ __forceinline__ Entry owner_entry(const Entry* __restrict__ tab, int ntens) {
+  return tab[owner_index(tab, ntens)];
 }
 
 // One fp32 operation, one rounding.  __fmul_rn / __fadd_rn are plain * and + compiled under the
@@ -246,6 +261,82 @@ __global__ __launch_bounds__(256) void l2_multi_final_kernel(const double* __res
   if (threadIdx.x == 0) out[0] = (float)((add_to ? (double)add_to[0] : 0.0) + red[0]);
 }
 
+// ---- LARS: per-tensor norms, trust ratios and the update, one block per 2048 elements -------------
+// (You, Gitman, Ginsburg 2017; optimisers/LARS.py.)  One table of LarsEntry rows drives all three.
+
+// Launch 1: part[2b] = sum of w^2, part[2b + 1] = sum of g^2 over block b's chunk, in fp64.
+__global__ __launch_bounds__(256) void lars_partial_kernel(const LarsEntry* __restrict__ tab, int ntens,
+                                                           double* __restrict__ part) {
+  __shared__ double red[2][256];
+  const LarsEntry e = owner_entry(tab, ntens);
+  chunk_sum_squares(e, e.w, red[0]);
+  chunk_sum_squares(e, e.g, red[1]);
+  if (threadIdx.x == 0) {
+    part[2 * (long long)blockIdx.x] = red[0][0];
+    part[2 * (long long)blockIdx.x + 1] = red[1][0];
+  }
+}
+
+// Launch 2, one block per tensor t: the fixed-order sums of the tensor's own partials (blocks
+// block0_t .. block0_{t+1}, the last row ending at total_blocks), then
+//   wn = (float)sqrt(sum w^2);  gn = (float)sqrt(sum g^2)
+//   ratio = (trust * wn) / ((gn + wd * wn) + eps)   for an adapted row with wn > 0 and gn > 0, else 1
+// and stats[4t .. 4t+3] = {wn, gn, ratio, 0}.  A non-finite norm is not special-cased.
+__global__ __launch_bounds__(256) void lars_final_kernel(const LarsEntry* __restrict__ tab, int ntens,
+                                                         long long total_blocks, const double* __restrict__ part,
+                                                         float trust, float wd, float eps,
+                                                         float* __restrict__ stats) {
+  __shared__ double red[2][256];
+  const int t = blockIdx.x;
+  const long long first = tab[t].block0;
+  const long long last = t + 1 < ntens ? tab[t + 1].block0 : total_blocks;
+  double sw = 0.0, sg = 0.0;
+  for (long long b = first + threadIdx.x; b < last; b += 256) {
+    sw += part[2 * b];
+    sg += part[2 * b + 1];
+  }
+  block_sum(red[0], sw);
+  block_sum(red[1], sg);
+  if (threadIdx.x == 0) {
+    const float wn = (float)sqrt(red[0][0]);
+    const float gn = (float)sqrt(red[1][0]);
+    float ratio = 1.0f;
+    if ((tab[t].flags & 1) && wn > 0.0f && gn > 0.0f)
+      ratio = __fdiv_rn(mul_1r(trust, wn), add_1r(add_1r(gn, mul_1r(wd, wn)), eps));
+    float* out = stats + 4 * (long long)t;
+    out[0] = wn;
+    out[1] = gn;
+    out[2] = ratio;
+    out[3] = 0.0f;
+  }
+}
+
+// Launch 3:  g' = g + wd * w (adapted rows, wd != 0);  step = (-lr) * ratio_t;
+//            d = step * g' + mom * v;  w += d;  v = d
+// SGD momentum's form and op order (SGDMomentum.py:33-39): a row that is not adapted has ratio 1, so
+// step is exactly -lr and its update is sgd_momentum_multi_kernel's bit for bit.  g and stats are
+// read only; w and v are written once each.
+__global__ __launch_bounds__(256) void lars_update_kernel(const LarsEntry* __restrict__ tab, int ntens, float lr,
+                                                          float mom, float wd, const float* __restrict__ stats) {
+  const int t = owner_index(tab, ntens);
+  const LarsEntry e = tab[t];
+  const float step = mul_1r(-lr, stats[4 * (long long)t + 2]);
+  const bool decay = (e.flags & 1) && wd != 0.0f;
+  const long long i0 = ((long long)blockIdx.x - e.block0) * kChunk;
+#pragma unroll
+  for (int k = 0; k < kChunk / 256; ++k) {
+    const long long i = i0 + k * 256 + threadIdx.x;
+    if (i < e.n) {
+      const float w = e.w[i];
+      float g = e.g[i];
+      if (decay) g = add_1r(g, mul_1r(wd, w));
+      const float d = add_1r(mul_1r(step, g), mul_1r(mom, e.v[i]));
+      e.w[i] = add_1r(w, d);
+      e.v[i] = d;
+    }
+  }
+}
+
 // ---- the C entries ---------------------------------------------------------------------------------
 // table: device array of ntens rows; total_blocks = the sum over the tensors of ceil(n / chunk), the
 // first_block of a virtual row ntens.  It is the grid, so it must fit one.
@@ -309,6 +400,35 @@ DK_API int dk_grad_norm_multi_f32(const void* table, int ntens, long long total_
   hipLaunchKernelGGL(grad_norm_final_kernel, dim3(1), dim3(256), 0, as_stream(stream),
                      static_cast<const double*>(ws), total_blocks, max_norm, out);
   return launch_status();
+}
+
+// LARS: launches 1 and 2 (the per-tensor norms and trust ratios), then launch 3 (the update).
+DK_API size_t dk_lars_workspace_bytes(long long total_blocks) {
+  return total_blocks > 0 ? (size_t)total_blocks * 2 * sizeof(double) : 0;
+}
+
+DK_API int dk_lars_norms_multi_f32(const void* table, int ntens, long long total_blocks, float trust,
+                                   float weight_decay, float eps, float* stats, void* ws, size_t ws_bytes,
+                                   void* stream) {
+  if (!table_args_ok(table, ntens, total_blocks) || !stats) return DK_ERR_ARGS;
+  if (ntens == 0) return 0;
+  if (total_blocks > 0 && (!ws || ws_bytes < dk_lars_workspace_bytes(total_blocks))) return DK_ERR_WORKSPACE;
+  const LarsEntry* tab = static_cast<const LarsEntry*>(table);
+  if (total_blocks > 0) {
+    hipLaunchKernelGGL(lars_partial_kernel, dim3((unsigned)total_blocks), dim3(256), 0, as_stream(stream), tab,
+                       ntens, static_cast<double*>(ws));
+    const int rc = launch_status();
+    if (rc) return rc;
+  }
+  hipLaunchKernelGGL(lars_final_kernel, dim3((unsigned)ntens), dim3(256), 0, as_stream(stream), tab, ntens,
+                     total_blocks, static_cast<const double*>(ws), trust, weight_decay, eps, stats);
+  return launch_status();
+}
+
+DK_API int dk_lars_multi_f32(const void* table, int ntens, long long total_blocks, float lr, float momentum,
+                             float weight_decay, const float* stats, void* stream) {
+  if (!stats) return DK_ERR_ARGS;
+  return launch_update(lars_update_kernel, table, ntens, total_blocks, stream, lr, momentum, weight_decay, stats);
 }
 
 // All l2 loss terms of a network in two launches:

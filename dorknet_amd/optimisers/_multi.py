@@ -21,7 +21,9 @@ dataset ``optimiser/<layer_name>/<param>`` per state tensor, in the parameter's 
 
 Adam (optimisers/Adam.py) is built on the same base with a wider row and state of its own: it
 overrides ``_init_state``, ``_entries`` and ``_state_items`` and names its integer attribute
-(``step_count``) in ``_COUNTERS``.
+(``step_count``) in ``_COUNTERS``.  LARS (optimisers/LARS.py) keeps SGDMomentum's state and adds a
+flags word to the row; its kernels take 2048 elements per block (``_PER_BLOCK``) and its update is
+three launches, so it overrides ``_entries`` and ``update_weights``.
 """
 from __future__ import annotations
 
@@ -57,6 +59,7 @@ class MultiTensorOptimiser:
     _COUNTERS = ()  # integer attributes of the state file (Adam's step_count)
     _HAS_STATE = True
     _POINTERS = 3  # w, g, state
+    _PER_BLOCK = 256  # elements per block of the class's kernels (LARS: 2048)
     _STATE_WORDS = ("parameters, grads and state", "grad / state")
 
     def __init__(self, network, learning_rate, update_skip_projections=False):
@@ -77,7 +80,7 @@ class MultiTensorOptimiser:
         self.learnable_layers = discover_learnable_layers(network, update_skip_projections)
         self.learning_rate = learning_rate
         self._init_state()
-        self._dev = DeviceTable(256, name, self._STATE_WORDS, self._POINTERS)
+        self._dev = DeviceTable(self._PER_BLOCK, name, self._STATE_WORDS, self._POINTERS)
 
     def _zero_state(self):
         """{layer: {param: zeros shaped like the gradient}}"""

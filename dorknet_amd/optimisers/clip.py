@@ -68,7 +68,7 @@ def clip_grad_norm(optimiser, max_norm):
     """Scale the gradients of ``optimiser.learnable_layers`` in place so that their global l2 norm is
     at most ``max_norm``; returns the norm before scaling as a 0-d device tensor (no host
     synchronisation: read it with ``float()`` only where a wait is acceptable).  Works for SGD,
-    SGDMomentum, RMSProp and Adam.
+    SGDMomentum, RMSProp, Adam and LARS.
 
     Under ``parallel.DataParallel`` call it after ``finish()``: the norm is then of the averaged
     gradients and bit-identical on every rank, so every rank applies the same scale."""

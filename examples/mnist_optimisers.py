@@ -1,5 +1,6 @@
 """The reference's three optimisers (optimisers/SGD.py, optimisers/SGDMomentum.py, optimisers/RMSProp.py)
-and Adam (an extension; here with decoupled weight decay 0.01 and global-norm clipping at 5) on
+and, as extensions, Adam (here with decoupled weight decay 0.01 and global-norm clipping at 5) and LARS
+(per-tensor trust ratios on the weights, weight decay 1e-4) on
 MNISTMaxPoolNet (examples/mnist_maxpool.py) over a fixed synthetic batch: U[0, 1) images with
 random labels, which the network memorises.  Prints the loss every few steps and, half way, saves
 the optimiser state (save_state_to_h5), builds a new optimiser and restores it (load_state_from_h5),
@@ -30,6 +31,7 @@ def synthetic_batch(batch, seed=0):
 
 def make_optimiser(which, net, lr=None):
     from dorknet_amd.optimisers.Adam import Adam
+    from dorknet_amd.optimisers.LARS import LARS
     from dorknet_amd.optimisers.RMSProp import RMSProp
     from dorknet_amd.optimisers.SGD import SGD
     from dorknet_amd.optimisers.SGDMomentum import SGDMomentum
@@ -39,6 +41,8 @@ def make_optimiser(which, net, lr=None):
         return SGDMomentum(net, 0.01 if lr is None else lr, 0.9)
     if which == "adam":
         return Adam(net, 0.001 if lr is None else lr, weight_decay=0.01, max_grad_norm=5.0)
+    if which == "lars":
+        return LARS(net, 0.02 if lr is None else lr, 0.9, trust_coefficient=0.25, weight_decay=1e-4)
     return RMSProp(net, 0.001 if lr is None else lr, 0.9)
 
 
@@ -47,7 +51,7 @@ def main():
     import torch
     from dorknet_amd._tensor import as_device
     ap = argparse.ArgumentParser()
-    ap.add_argument("--optimiser", choices=["sgd", "sgdmomentum", "rmsprop", "adam"], default="rmsprop")
+    ap.add_argument("--optimiser", choices=["sgd", "sgdmomentum", "rmsprop", "adam", "lars"], default="rmsprop")
     ap.add_argument("--batch", type=int, default=64)
     ap.add_argument("--steps", type=int, default=40)
     ap.add_argument("--lr", type=float, default=None)

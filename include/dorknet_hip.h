@@ -661,6 +661,27 @@ int dk_softmax_xent_bwd_f32(const float* p, const float* y_onehot, int B, int K,
  *                            (torch's clip_grad_norm_); max_norm <= 0 or infinite: out[1] = 1.
  *                            ws: dk_grad_norm_workspace_bytes(total_blocks), else DK_ERR_WORKSPACE.
  *     dk_grad_scale_multi_f32: g = scale[0] * g in place, one rounding; a scale of 1 writes nothing.
+ *   LARS (You, Gitman, Ginsburg 2017; no optimiser of the reference): momentum SGD whose step is scaled per
+ *   tensor by a trust ratio.  One table drives its three launches, 48 bytes per entry:
+ *   { float* w; const float* g; float* v; int64 n; int64 first_block; int64 flags }, first_block = sum of
+ *   ceil(n / 2048) over the preceding entries, flags bit 0 = adapt.  The caller forms trust, weight_decay,
+ *   eps, lr and momentum in double; each is rounded to fp32 once.
+ *     dk_lars_norms_multi_f32: launch 1 writes two fp64 partials per block (sum w^2, sum g^2 over its 2048
+ *                            elements), launch 2 (one block per entry t) adds the entry's own partials in a
+ *                            fixed order and writes stats[4t .. 4t+3] = { wn, gn, ratio, 0 } with
+ *                            wn = (float)sqrt(sum w^2), gn = (float)sqrt(sum g^2) and, one fp32 rounding per
+ *                            operation, ratio = (trust * wn) / ((gn + weight_decay * wn) + eps) for an
+ *                            adapted entry with wn > 0 and gn > 0, else 1.  A non-finite norm propagates.
+ *                            w, g and v are not written.  stats: 4 floats per entry (NULL: DK_ERR_ARGS);
+ *                            ws: dk_lars_workspace_bytes(total_blocks) = 16 bytes per block, else
+ *                            DK_ERR_WORKSPACE.  Bit-identical from run to run.
+ *     dk_lars_multi_f32:     launch 3, per element, each operation rounded once to fp32, in this order:
+ *                            g' = g + weight_decay * w   (only for adapted entries and weight_decay != 0)
+ *                            step = (-lr) * stats[4t+2];  d = step * g' + momentum * v;  w = w + d;  v = d
+ *                            An entry that is not adapted has ratio 1 and gets dk_sgd_momentum_multi_f32's
+ *                            update (grad_scale 1) bit for bit.  g and stats are read only (stats NULL:
+ *                            DK_ERR_ARGS); w and v are written once.
+ *   Table, count and grid errors as above; ntens == 0 returns 0.
  *   l2 loss term: regularisers/l2.py:12-14; scale: l2.py:16-17 and DP averaging.  dk_l2_loss_multi_f32 adds
  *   all of a network's terms in two launches: out[0] = add_to[0] (may be NULL) + sum_t 0.5 * strength_t *
  *   sum(w_t^2) over table entries { const float* w; int64 n; int64 first_block; float strength; float pad }
@@ -675,6 +696,9 @@ int dk_adam_multi_f32(const void* table, int ntens, long long total_blocks, floa
 size_t dk_grad_norm_workspace_bytes(long long total_blocks);
 int dk_grad_norm_multi_f32(const void* table, int ntens, long long total_blocks, float max_norm, float* out, void* ws, size_t ws_bytes, void* stream);
 int dk_grad_scale_multi_f32(const void* table, int ntens, long long total_blocks, const float* scale, void* stream);
+size_t dk_lars_workspace_bytes(long long total_blocks);
+int dk_lars_norms_multi_f32(const void* table, int ntens, long long total_blocks, float trust, float weight_decay, float eps, float* stats, void* ws, size_t ws_bytes, void* stream);
+int dk_lars_multi_f32(const void* table, int ntens, long long total_blocks, float lr, float momentum, float weight_decay, const float* stats, void* stream);
 int dk_l2_loss_f32(const float* w, long long n, float strength, int accumulate, float* out, void* stream);
 size_t dk_l2_multi_workspace_bytes(long long total_blocks);
 int dk_l2_loss_multi_f32(const void* table, int ntens, long long total_blocks, const float* add_to, float* out, void* ws, size_t ws_bytes, void* stream);

@@ -1,7 +1,7 @@
-"""fp64 reference of the dense convolution and the per-element error bounds its fp32 kernels are held to
-(tests/test_conv_ref_host.py, tests/test_gpu_conv_elementwise.py).  Host only: numpy + torch-CPU, nothing from
-dorknet_amd, no GPU call.  The pieces shared with the depthwise and pointwise references come from
-tests/_dw_ref.py and tests/_pw_ref.py.
+"""fp64 reference of the dense convolution and the per-element error bounds its fp32 and bf16 kernels are held to
+(tests/test_conv_ref_host.py, tests/test_gpu_conv_elementwise.py, tests/test_gpu_conv_bf16_elementwise.py).  Host
+only: numpy + torch-CPU, nothing from dorknet_amd, no GPU call.  The pieces shared with the depthwise and pointwise
+references come from tests/_dw_ref.py and tests/_pw_ref.py.
 
 Operation (layers/convolution.py; oracle.ref.conv_forward / conv_backward), OH = (H + 2 pad - R) // stride + 1:
     a  = bn(x) (+ ReLU) where an input BatchNorm is applied on load, else x; zero padding AFTER the BatchNorm
@@ -43,6 +43,31 @@ Bounds on |got - ref| per element, none excluded, none fitted to a kernel's outp
     statistics  _pw_ref.stats_checks: (1) against fp64 sums of what the same call stored:
         2^-53 (M + rows + 2) sum |term|; (2) against the reference sums: the summed per-element bounds.
         (engine: EpStoreStats on kRowConv tiles, gemm_engine.h:1414-1418; narrow: conv_narrow.hip:193-195, :205-211.)
+
+bf16 mode (bf16=True: dk_conv2d_{fwd_ex,dgrad,dgrad_phase,wgrad,wgrad_bnx}_bf16, gemm_bf16.hip:213-302; every GEMM on
+v_mfma_f32_32x32x16_bf16, gemm_engine.h:930-943).  The rules are those of tests/_pw_ref.py, quoted:
+    weights   "The reference uses wq = rne_bf16(w) EXACTLY in y and dx (the rounding of a given fp32 weight is
+              unambiguous)"; "the weights do not enter [the weight gradient] except in l2 w, which uses the fp32 w".
+    operands  "raw bf16 activations and a raw bf16 dy are exact; an operand formed on load (the BatchNorm output ...)
+              is a bf16 rounding of an fp32 value within e of the fp64 value, error scale 2^-8 (|v| + e) + e
+              (operand_err)".  ReLU commutes with the rounding (both monotone, 0 fixed).
+    padding   exactly 0 AFTER the BatchNorm (gemm_bf16.hip:219-222: each 4-group takes its own tap's bounds test and
+              the BatchNorm transforms in-image elements only); the zero padded channel of Cp > C is in the image, so
+              it is normalised to its own bn(0) != 0 (beta != 0): it meets zero weights in y and must be dropped by
+              the weight gradient's Cp -> C compaction.
+    y, dx     A = STEP (n + 3) twin + E as above with the fp32 accumulation, n the padded reduction length the
+              bf16 kernel runs: Ktot zero-filled (k >= Ktot loads 0, gemm_engine.h:241, :326) to whole k-tiles
+              (:856) of BK / 16 MFMAs (:932); BK is 16 (row configs 6, 14) or 32 (8, 15, 16), so n = roundup32(Ktot)
+              covers every route.  Zero products add no rounding; the padding is counted all the same.
+                forward          Ktot = R S Cp                (gemm_bf16.hip:242)
+                dk_conv2d_dgrad  Ktot = R S K                 (gemm_engine.h:1486)
+                phase dgrad      Ktot = Rp Sp Kp of the phase (gemm_engine.h:1512); no taps: n = 0, twin = 0, exact 0
+              The store is one RNE (rnd4<bf16_t> in EpStoreT::value4, gemm_engine.h:577-581; st4 of EpPhaseT, :797-799),
+              held to bf16_bound(ref, A) -- the interval form -- and to bf16_closed(ref, A): Ref.b16 / Ref.b16c.
+    dw        fp32 (split-K slabs and their reduce as for fp32): the fp32 form with the rounded operands' scales,
+              STEP (M + 2) dwa + 2 u |ref| + wgrad(|dy|, operand_err(a, ea, True)); a raw bf16 dy is exact.
+    statistics  stats_checks unchanged, over the bf16 values the call stored (EpStoreStatsT<bf16_t> accumulates the
+              rounded value4, gemm_engine.h:606-614) and against the reference with the summed b16 bounds.
 No kernel output has moved any constant above.
 
 ReLU masks: the inputs are chosen (SEEDS) so that _dw_ref.mask_margin > 1 for the input BatchNorm (on x) and the
@@ -58,6 +83,13 @@ Tile and route rules the case tables cite, as read from the code:
         kRowPlain: reduction <= 128 -> 6, else 8.
     split-K (gemm_engine.h:1266-1281): K <= 64 < R S Cp -> config 6 (64 x 128 x 32), else config 1 (64 x 64 x 32);
         splits = min(ceil(1024 / tiles), ceil(M / 32)) (:1289-1297): M <= 32 pixels is a single split.
+    bf16 row tiles (gemm_engine.h:1209-1222, then the fp32 rules :1234-1237; forward and both dgrads are kRowConv,
+        gemm_bf16.hip:243, :252, :264; "columns" are K for the forward and C for the dgrads, the reduction is R S Cp,
+        R S K or the phase's Rp Sp Kp): reduction > 128 -> config 16 (128 x 128 x 32, 8 waves) with >= 128 columns, else
+        config 15 (128 x 64 x 32); reduction <= 128 -> config 14 (128 x 64 x 16) with <= 64 columns, else config 6
+        (64 x 64 x 16).  No bf16 convolution picks config 8 (64 x 64 x 32).
+    bf16 split-K (gemm_engine.h:1265-1275): K >= 128 and R S Cp >= 128 -> config 4 (128 x 128 x 32); K <= 64 < R S Cp
+        -> config 6 (64 x 128 x 32); else config 1 (64 x 64 x 32); the splits as for fp32.
     narrow (conv_narrow.hip:394-423): shapes (C,R,S,stride) in (3,5,5,2) (3,7,7,2) (3,3,3,1) (3,3,3,2) (1,3,3,1) (1,5,5,1);
         4 <= K <= 64, K % 4 == 0; forward T = ceil(OW / 16) in 1..8; quads(OW) buckets {4, 8, 16, 28, 32} of
         ceil(OW / 4); staged columns st (16 T - 1) + S and st (4 quads - 1) + S at most 256: at stride 2 that is
@@ -83,35 +115,67 @@ Case = collections.namedtuple("Case", "C Cp R S stride pad N H W K")
 ENGINE = {
     # 3x3 s1 p1; R S Cp = 72 <= 128, K = 24 <= 64: row config 14; M = 286 ragged for 128 (2 tiles + 30); K no multiple
     # of 16; split-K config 6 (K <= 64 < 72), 9 splits of 32 pixels, the last ragged (30); odd H != W
+    # bf16: forward row config 14, dgrads config 15 (R S K = 216 > 128, C = 8 < 128), split-K config 6
     "e1": Case(8, 8, 3, 3, 1, 1, 2, 13, 11, 24),
     # 3x3 s1 p0; R S Cp = 108 <= 128, K = 72 > 64: row config 6; M = 198 = 3 x 64 + 6; ragged second column tile (72);
     # Cp = 12: 16-wide k-tiles cross tap boundaries, the last is ragged (108 = 6 x 16 + 12); split-K config 1
+    # bf16: forward row config 6, stride-1 / phase dgrad config 15 (C = 12: every other dx row 8 bytes off a 16-byte
+    # boundary), split-K config 1
     "e2": Case(12, 12, 3, 3, 1, 0, 2, 13, 11, 72),
     # 4x4 s2 p1; R S Cp = 128: config 14; M = 60 < one tile; (H + 2 pad - R) % 2 = 1 (the remainder is the bottom
     # padding row: every input row is still read, see e12)
+    # bf16: forward config 14; phases of 2 x 2 taps, R S Kp = 96: config 14; split-K config 6
     "e3": Case(8, 8, 4, 4, 2, 1, 2, 13, 11, 24),
     # 5x5 s2 p1, C = 3 in Cp = 4 (the stem on the engine): config 14; M = 256 = exactly two 128-row tiles; scalar
     # EpPhase store (C % 4 != 0); the wgrad reduce compacts Cp -> C
+    # bf16: forward config 14; phases of 4 .. 9 taps x 64: config 15, 6-byte pixels (scalar store); split-K config 6
     "e4": Case(3, 4, 5, 5, 2, 1, 4, 17, 17, 64),
     # 7x7 s2 p3, C = 3 in Cp = 4; R S Cp = 196 > 128: row config 8; M = 96 = 64 + 32 ragged; split-K config 6
+    # bf16: forward config 15 (R S Cp = 196 > 128, K < 128); phases of 9 .. 16 taps x 24: config 15; split-K config 6
     "e5": Case(3, 4, 7, 7, 2, 3, 2, 15, 11, 24),
     # 1x1 s2 p0: three of the four dx phases have no taps and must be written as exact zeros
+    # bf16: config 14 throughout (the empty phases run it with no k-tile); split-K config 1 (R S Cp = 8 <= 64)
     "e6": Case(8, 8, 1, 1, 2, 0, 2, 9, 7, 24),
     # 4x4 s3 p2 on 17 x 13: ragged phases (6 / 6 / 5 rows, 5 / 4 / 4 columns); (H + 2 pad - R) % 3 = 2
+    # bf16: forward config 14 (R S Cp = 128); phases of 1 / 2 / 4 taps x 24: config 14; split-K config 6
     "e7": Case(8, 8, 4, 4, 3, 2, 2, 17, 13, 24),
     # 3x3 s1 pad = R - 1 = 2: the output (7 x 8) is larger than the input (5 x 6); K = 72: config 6; M = 56 < one tile
+    # bf16: forward config 6, dgrads config 15, split-K config 1
     "e8": Case(8, 8, 3, 3, 1, 2, 1, 5, 6, 72),
     # 3x3 s1 p1, R S Cp = 144 > 128 with K = 72: row config 8, two column tiles; M = 128 = exactly two 64-row tiles;
     # split-K config 1 (the other branch) with 4 whole splits
+    # bf16: forward config 15 (144 > 128, K = 72 < 128), dgrads config 15, split-K config 1
     "e9": Case(16, 16, 3, 3, 1, 1, 2, 8, 8, 72),
     # M = 30 <= 32 pixels: a single split-K split; one partial row tile
+    # bf16: as e1 (14 / 15 / split-K config 6, one split)
     "e10": Case(8, 8, 3, 3, 1, 1, 1, 5, 6, 24),
     # K = 6 (K % 4 != 0: dy zero-padded to Kp = 8 for the phase dgrad, scalar dy loads in the weight gradient) and
     # C = 3 in Cp = 4 at stride 1
+    # bf16: the forward, the stride-1 dgrad and the weight gradients refuse K % 4 != 0; the phase dgrad takes K = 6 in
+    # Kp = 8 (reduction 72, config 14) and stores 6-byte pixels
     "e11": Case(3, 4, 3, 3, 1, 1, 2, 7, 5, 6),
     # 3x3 s2 p0 on 12 x 10: (H - R) % 2 = 1 > pad: the last dx row and column are never read by the forward and
     # must be written as exact zeros
+    # bf16: config 14 throughout (phase reductions 96 / 48 / 48 / 24); split-K config 6
     "e12": Case(8, 8, 3, 3, 2, 0, 2, 12, 10, 24),
+}
+
+# Engine cases for what ENGINE does not reach under the bf16 rules (bf16 row configs 16 and, in a dgrad, 6; split-K
+# config 4; K % 8 == 4).  Run in bf16 by tests/test_gpu_conv_bf16_elementwise.py, in both modes on the host.
+ENGINE16 = {
+    # 3x3 s1 p1, R S Cp = 144 > 128 with K = 128: forward row config 16 (128 x 128 x 32, 8 waves); M = 162 = 128 + 34
+    # ragged: 2 statistics rows, 3 on 64-row tiles; split-K config 4 (K >= 128, R S Cp >= 128: 128 x 128 tiles, the
+    # second column tile ragged, 144 = 128 + 16), 6 splits, the last ragged (162 = 5 x 32 + 2); dgrads config 15
+    "h1": Case(16, 16, 3, 3, 1, 1, 2, 9, 9, 128),
+    # the mirror image: C = 128 with R S K = 144 > 128: both dgrads on row config 16; the forward on config 15 with
+    # its longest reduction (R S Cp = 1152: 36 k-tiles); split-K config 6 over nine 128-column tiles
+    "h2": Case(128, 128, 3, 3, 1, 1, 2, 9, 9, 16),
+    # K = 20 (K % 8 == 4): 40-byte y and dy rows, every other one 8 bytes off a 16-byte boundary; 3x3 s2 p1 on
+    # 13 x 11: M = 84, phases of 1 / 2 / 2 / 4 taps; config 14 throughout, split-K config 6
+    "h3": Case(8, 8, 3, 3, 2, 1, 2, 13, 11, 20),
+    # C = 72 > 64 with R S K = 72 <= 128: both dgrads on row config 6 (64 x 64 x 16), which ENGINE reaches in the
+    # forward only; a ragged second column tile (72 = 64 + 8); M = 30 < one tile; forward config 15, split-K config 6
+    "h4": Case(72, 72, 3, 3, 1, 1, 1, 5, 6, 8),
 }
 
 # Narrow cases (conv_narrow.hip); T = ceil(OW / 16), q = ceil(OW / 4) -> quads bucket.
@@ -161,7 +225,7 @@ SUBPIX = {
     "s7": Case(16, 16, 2, 2, 2, 0, 1, 7, 5, 16),
 }
 
-CASES = {**ENGINE, **NARROW, **SUBPIX}
+CASES = {**ENGINE, **NARROW, **SUBPIX, **ENGINE16}   # (ENGINE16 last: a case's inputs follow from its position)
 ORDER = list(CASES)
 
 # The seed of each case: the first of 0, 1, 2, ... at which mask_margin > 1 holds for the input BatchNorm (on x)
@@ -257,48 +321,67 @@ def widen_lattice(g2, OH, OW):
     return g
 
 
+def roundup32(v):
+    return -(-v // 32) * 32
+
+
 class Ref:
-    """Result and bound of one call."""
+    """Result and bound of one call: ref, A (the fp32 bound; in bf16 mode the bound on the value before the store),
+    and in bf16 mode of y / dx b16 / b16c, the bf16 store's bounds (interval / closed form)."""
 
-    def __init__(self, ref, A):
+    def __init__(self, ref, A, stored16=False):
         self.ref, self.A = ref, A
+        if stored16:
+            self.b16, self.b16c = P.bf16_bound(ref, A), P.bf16_closed(ref, A)
+
+    def bound(self, bf16):
+        return self.b16 if bf16 else self.A
 
 
-def forward(d, bias=False, bn=None, narrow=False):
-    """y and its bound.  bn: None / 0 / 1 = the input BatchNorm off / without / with ReLU.  Also .a / .ea."""
+def forward(d, bias=False, bn=None, narrow=False, bf16=False):
+    """y and its bound.  bn: None / 0 / 1 = the input BatchNorm off / without / with ReLU.  Also .a / .ea: the operand
+    and its error scale as the MFMA sees it.  bf16: the engine's bf16 entry (module docstring)."""
     c = d["case"]
+    assert not (narrow and bf16)
     a, ea, _ = bn_operand(d["x"], pi_of(d, bn))
-    w = d["w"].astype(np.float64)
+    ea = P.operand_err(a, ea, bf16 and bn is not None)
+    w = P.weights(d["w"], bf16)
     y, ya = conv(a, w, c.stride, c.pad), conv(np.abs(a), np.abs(w), c.stride, c.pad)
     if bias:
         b64 = d["bias"].astype(np.float64)[None, :, None, None]
         y, ya = y + b64, ya + np.abs(b64)
     n = roundup4(c.C * c.R * c.S) if narrow else c.R * c.S * c.Cp
-    o = Ref(y, STEP * (n + 3) * ya + conv(ea, np.abs(w), c.stride, c.pad))
+    if bf16:
+        n = roundup32(n)
+    o = Ref(y, STEP * (n + 3) * ya + conv(ea, np.abs(w), c.stride, c.pad), bf16)
     o.a, o.ea = a, ea
     return o
 
 
-def dgrad(d, entry):
-    """dx (N,C,H,W) and its bound; entry: "gemm" (dk_conv2d_dgrad_f32), "phase", "subpixel"."""
+def dgrad(d, entry, bf16=False):
+    """dx (N,C,H,W) and its bound; entry: "gemm" (dk_conv2d_dgrad_f32 / _bf16), "phase", "subpixel" (fp32 only)."""
     c = d["case"]
-    w = d["w"].astype(np.float64)
+    w = P.weights(d["w"], bf16)
+    pad32 = roundup32 if bf16 else (lambda v: v)
     dx = conv_dx(d["dy"], w, c.stride, c.pad, c.H, c.W)
     dxa = conv_dx(np.abs(d["dy"]), np.abs(w), c.stride, c.pad, c.H, c.W)
     if entry == "gemm":
         assert c.stride == 1
-        return Ref(dx, STEP * (c.R * c.S * c.K + 3) * dxa)
+        return Ref(dx, STEP * (pad32(c.R * c.S * c.K) + 3) * dxa, bf16)
     taps = taps_map(c)[None, None]
     if entry == "phase":
-        return Ref(dx, STEP * (taps * roundup4(c.K) + 3) * dxa)
-    assert entry == "subpixel"
+        return Ref(dx, STEP * (pad32(taps * roundup4(c.K)) + 3) * dxa, bf16)
+    assert entry == "subpixel" and not bf16
     return Ref(dx, U * (taps * c.K + 2) * dxa)
 
 
-def wgrad(d, l2=0.0, bn=None, dy=None, ed=None):
-    """dw (K,C,R,S) and its bound; dy / ed: the gradient formed on load and its error scale (default: d["dy"])."""
+def wgrad(d, l2=0.0, bn=None, dy=None, ed=None, bf16=False):
+    """dw (K,C,R,S), fp32 in both modes, and its bound; dy / ed: the gradient formed on load and its error scale
+    (default: d["dy"]; fp32 only).  bf16: the operand a of a BatchNorm on load is rounded to bf16."""
     c = d["case"]
+    assert not (bf16 and dy is not None)
     a, ea, _ = bn_operand(d["x"], pi_of(d, bn))
+    ea = P.operand_err(a, ea, bf16 and bn is not None)
     dy = d["dy"] if dy is None else dy
     shape = d["w"].shape
     dw = conv_dw(dy, a, shape, c.stride, c.pad) + l2 * d["w"].astype(np.float64)

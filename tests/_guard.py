@@ -1,6 +1,6 @@
 """Guarded outputs for the per-element kernel tests (tests/test_gpu_dw_elementwise.py,
-tests/test_gpu_pw_elementwise.py, tests/test_gpu_conv_elementwise.py, tests/test_gpu_bn_elementwise.py,
-tests/test_gpu_head_elementwise.py): a 16-byte-aligned slice of a larger allocation pre-filled with a NaN bit pattern.
+tests/test_gpu_pw_elementwise.py, tests/test_gpu_conv_elementwise.py, tests/test_gpu_conv_bf16_elementwise.py,
+tests/test_gpu_bn_elementwise.py, tests/test_gpu_head_elementwise.py): a 16-byte-aligned slice of a larger allocation pre-filled with a NaN bit pattern.
 The 64-element margins before and after must stay bitwise untouched (a 16-byte store past a ragged row) and no output
 element may remain NaN (an element never written).
 

@@ -15,6 +15,7 @@
 // rows (pixels); thread (cg, pl) owns channel group cg (V = 4 channels, one float4) and
 // walks rows pl, pl + PL, ... with four rows of loads in flight.  Per-channel
 // parameters live in registers, so there is no per-element index arithmetic.
+#include "act_math.h"
 #include "dk_common.h"
 #include "fold_tail.h"
 
@@ -917,6 +918,147 @@ DK_API int dk_relu_bwd_bn_partial_bf16(const bf16_t* dy, const uint8_t* mask, co
                                        int relu, bf16_t* dx, void* part, size_t part_bytes, void* stream) {
   if (!dy || !mask || !x || !dx || P < 1 || C < 4 || C % 4) return DK_ERR_ARGS;
   return relu_bwd_bn_partial_t(dy, mask, x, P, C, mean, invstd, gamma, beta, relu, dx, part, part_bytes, stream);
+}
+
+// ---------------------------------------------------------------------------------------
+// Backward of an activation beyond ReLU (act_math.h; activations.hip) that took this BN's output on
+// load, fused with stage 1 of this BN's backward -- dk_relu_bwd_bn_partial_*'s pass with the mask
+// replaced by act'(v): v = bn_relu_out(x) is recomputed (for bf16 rounded to bf16, as the forward's
+// dk_act_fwd_bnx_bf16 had it), g = dy * act'(v), zeroed where a fused ReLU killed v, is stored once
+// (bf16: one rounding) and part[nblk][2][C] = (sum g, sum g * x_hat) runs over the stored g.  Same row
+// geometry, 32-group cap, reduction order and fold tail as bn_bwd_partial_kernel<V, true, E>.
+// ---------------------------------------------------------------------------------------
+namespace dk {
+
+template <int V, class E = float>
+__global__ __launch_bounds__(256) void act_bwd_bn_partial_kernel(const E* __restrict__ x, const E* __restrict__ dy,
+                                                                 int P, int C, int ppb,
+                                                                 const float* __restrict__ mean,
+                                                                 const float* __restrict__ invstd,
+                                                                 const float* __restrict__ gamma,
+                                                                 const float* __restrict__ beta, int relu, int kind,
+                                                                 float alpha, E* __restrict__ gout,
+                                                                 double* __restrict__ part, FoldTail ft, int cgt_cap) {
+  using VT = VecT<V, E>;
+  __shared__ double red[2][256][V];
+  const RowGeom g = row_geom(C, V, cgt_cap);
+  const int tid = threadIdx.x;
+  const int cg = blockIdx.y * g.cgt + tid % g.cgt;
+  const int pl = tid / g.cgt;
+  const bool active = pl < g.PL && cg < g.CG;
+  const int p0 = blockIdx.x * ppb, p1 = min(P, p0 + ppb);
+  double s[V], q[V];
+  float mu[V], is[V], ga[V], be[V];
+  const int c0 = active ? cg * V : 0;
+#pragma unroll
+  for (int e = 0; e < V; ++e) {
+    s[e] = q[e] = 0.0;
+    mu[e] = mean[c0 + e];
+    is[e] = invstd[c0 + e];
+    ga[e] = gamma[c0 + e];
+    be[e] = beta[c0 + e];
+  }
+  // one group of V elements: g stored, its kept value and x_hat accumulated
+  auto one = [&](typename VT::T xv, typename VT::T dv, size_t off) {
+    typename VT::T gv;
+#pragma unroll
+    for (int e = 0; e < V; ++e) {
+      const float r = bn_out(el(xv, e), mu[e], is[e], ga[e], be[e]);
+      const bool dead = relu && !(r > 0.f);
+      const float v = rnd1<E>(dead ? 0.f : r);
+      set_el(gv, e, dead ? 0.f : act_grad(kind, alpha, v, el(dv, e)));
+    }
+    VT::store(gout + off, gv);
+    const typename VT::T kept = VT::stored(gv);
+#pragma unroll
+    for (int e = 0; e < V; ++e) {
+      const float ge = el(kept, e);
+      const float xh = (el(xv, e) - mu[e]) * is[e];
+      s[e] += (double)ge;
+      q[e] += (double)ge * (double)xh;
+    }
+  };
+  if (active) {
+    const int PL = g.PL;
+    int p = p0 + pl;
+    for (; p + 3 * PL < p1; p += 4 * PL) {
+      typename VT::T xv[4], dv[4];
+#pragma unroll
+      for (int u = 0; u < 4; ++u) {
+        const size_t off = (size_t)(p + u * PL) * C + c0;
+        xv[u] = VT::load(x + off);
+        dv[u] = VT::load(dy + off);
+      }
+#pragma unroll
+      for (int u = 0; u < 4; ++u) one(xv[u], dv[u], (size_t)(p + u * PL) * C + c0);
+    }
+    for (; p < p1; p += PL) {
+      const size_t off = (size_t)p * C + c0;
+      one(VT::load(x + off), VT::load(dy + off), off);
+    }
+  }
+#pragma unroll
+  for (int e = 0; e < V; ++e) {
+    red[0][tid][e] = s[e];
+    red[1][tid][e] = q[e];
+  }
+  __syncthreads();
+  const int items = 2 * g.cgt * V;
+  for (int it = tid; it < items; it += 256) {
+    const int e = it % V;
+    const int gg = (it / V) % g.cgt;
+    const int which = it / (V * g.cgt);
+    const int cgg = blockIdx.y * g.cgt + gg;
+    if (cgg >= g.CG) continue;
+    double a = 0.0;
+    for (int qq = 0; qq < g.PL; ++qq) a += red[which][qq * g.cgt + gg][e];
+    pub_store(part + ((size_t)blockIdx.x * 2 + which) * C + cgg * V + e, a);
+  }
+  if (ft.part) {
+    const int cs = blockIdx.y * g.cgt * V;
+    fold_tail<256>(ft, blockIdx.x, cs, min(g.cgt * V, C - cs), blockIdx.y);
+  }
+}
+
+template <class E>
+static int act_bwd_bnx_t(const E* x, const E* dy, int P, int C, const float* mean, const float* invstd,
+                         const float* gamma, const float* beta, int relu, int kind, float alpha, E* gout, void* part,
+                         size_t part_bytes, void* stream) {
+  if (!x || !dy || !gout || !part || !mean || !invstd || !gamma || !beta || P < 1 || C < 1) return DK_ERR_ARGS;
+  if (kind < 0 || kind >= kNumActKinds || !(alpha - alpha == 0.f)) return DK_ERR_ARGS;
+  if (part_bytes < dk_bn_workspace_bytes(P, C)) return DK_ERR_WORKSPACE;
+  const int nblk = bn_blocks(P, C);
+  const int ppb = cdiv(P, nblk);
+  const bool vec = vec_ok_e(x, C) && vec_ok_e(dy, C) && vec_ok_e(gout, C);
+  if (!vec && sizeof(E) != 4) return DK_ERR_ARGS;
+  const int cap = 32;  // as relu_bwd_bn_partial_t: more pixel lanes per block at wide C
+  const RowGeom g = row_geom(C, vec ? 4 : 1, cap);
+  const dim3 grid(nblk, cdiv(g.CG, g.cgt));
+  FoldTail ft;  // an armed in-launch fold of the partial rows (fold_tail.h)
+  if (!fold_take(part, nblk, C, (int)grid.y, &ft) || ((g.cgt * (vec ? 4 : 1)) & 1)) ft.part = nullptr;
+  if (vec)
+    hipLaunchKernelGGL((act_bwd_bn_partial_kernel<4, E>), grid, dim3(256), 0, as_stream(stream), x, dy, P, C, ppb, mean,
+                       invstd, gamma, beta, relu, kind, alpha, gout, static_cast<double*>(part), ft, cap);
+  else
+    hipLaunchKernelGGL((act_bwd_bn_partial_kernel<1, E>), grid, dim3(256), 0, as_stream(stream), x, dy, P, C, ppb, mean,
+                       invstd, gamma, beta, relu, kind, alpha, gout, static_cast<double*>(part), ft, cap);
+  return fold_status(launch_status(), ft);
+}
+
+}  // namespace dk
+
+DK_API int dk_act_bwd_bnx_f32(const float* x, const float* dy, int P, int C, const float* bn_mean,
+                              const float* bn_invstd, const float* bn_gamma, const float* bn_beta, int bn_relu,
+                              int kind, float alpha, float* g, void* part, size_t part_bytes, void* stream) {
+  return act_bwd_bnx_t(x, dy, P, C, bn_mean, bn_invstd, bn_gamma, bn_beta, bn_relu, kind, alpha, g, part, part_bytes,
+                       stream);
+}
+DK_API int dk_act_bwd_bnx_bf16(const uint16_t* x, const uint16_t* dy, int P, int C, const float* bn_mean,
+                               const float* bn_invstd, const float* bn_gamma, const float* bn_beta, int bn_relu,
+                               int kind, float alpha, uint16_t* g, void* part, size_t part_bytes, void* stream) {
+  if (C < 4 || C % 4) return DK_ERR_ARGS;
+  return act_bwd_bnx_t(x, dy, P, C, bn_mean, bn_invstd, bn_gamma, bn_beta, bn_relu, kind, alpha, g, part, part_bytes,
+                       stream);
 }
 
 // Backward stage 2 from partials of any origin (dk_bn_bwd_partial_f64, a consumer's

@@ -1,4 +1,5 @@
-"""ReLU (reference: layers/activations.py).
+"""ReLU (reference: layers/activations.py), and four activations the reference lacks: LeakyReLu,
+ReLu6, HardSwish and SiLu (below ReLu).
 
 ``out = max(0, X)``; the backward mask is ``out > 0`` (gradient 0 at 0, :41).  The mask
 is kept as uint8 (the reference stores an fp32 copy, :42); ``positive_locs`` still
@@ -8,11 +9,14 @@ layer only records its output.
 """
 from __future__ import annotations
 
+import math
+import numbers
+
 import torch
 
 from .._hip import lib, stream_handle
-from .._tensor import act_dtype, as_device, empty_nhwc, is_nhwc as is_nhwc_t, rows, to_nhwc
-from ._bn_input import BNOut, JoinOut, Partials
+from .._tensor import BF16, act_dtype, as_device, empty_nhwc, is_nhwc as is_nhwc_t, rows, to_nhwc
+from ._bn_input import BNOut, JoinOut, Partials, lattice_tag
 from .layer import Layer
 
 
@@ -216,3 +220,151 @@ class ReLu(Layer):
 
     def load_from_h5(self, open_f, load_grads=True):
         pass
+
+
+# ---------------------------------------------------------------------------------------------
+# Activations beyond ReLU: extensions, the reference has only ReLu.  dk_act_* (dorknet_amd/csrc/
+# act_math.h, activations.hip, batchnorm.hip), DESIGN.md section 23.
+# ---------------------------------------------------------------------------------------------
+
+# the `kind` argument of the dk_act_* entries
+ACT_LEAKY, ACT_RELU6, ACT_HARDSWISH, ACT_SILU = 0, 1, 2, 3
+
+# per storage type: the forward (plain, BatchNorm on load) and the backward (plain, with stage 1 of the
+# BatchNorm's backward)
+_ACT_FWD = {torch.float32: ("dk_act_fwd_f32", "dk_act_fwd_bnx_f32"), BF16: ("dk_act_fwd_bf16", "dk_act_fwd_bnx_bf16")}
+_ACT_BWD = {torch.float32: ("dk_act_bwd_f32", "dk_act_bwd_bnx_f32"), BF16: ("dk_act_bwd_bf16", "dk_act_bwd_bnx_bf16")}
+
+
+_F32_MAX = 3.4028234663852886e38  # alpha travels as a C float
+
+
+def checked_alpha(layer_name, alpha):
+    """`alpha` (LeakyReLu's slope for v <= 0) as a finite float."""
+    if isinstance(alpha, bool) or not isinstance(alpha, numbers.Real):
+        raise TypeError("LeakyReLu({}): alpha must be a number, got {!r}".format(layer_name, alpha))
+    alpha = float(alpha)
+    if not math.isfinite(alpha) or abs(alpha) > _F32_MAX:  # (a NaN fails isfinite)
+        raise ValueError("LeakyReLu({}): alpha must be a finite fp32 value, got {!r}".format(layer_name, alpha))
+    return alpha
+
+
+class _Activation(Layer):
+    """An elementwise activation y = act(v) whose backward recomputes act'(v) from the layer's input:
+    no mask and no copy are stored, a training forward keeps only a reference to its input -- the
+    tensor, or the BNOut of a BatchNormLayer [+ ReLu] in front (applied on load, layers/_bn_input.py).
+    After a BNOut forward the backward also writes stage 1 of that BatchNorm's backward (Partials), so
+    BatchNorm + activation costs one read and one write forward, two reads and one write backward.
+    fp32 rows, fp32 or bf16 maps; the output has the input's shape and storage type."""
+    accepts_bn_input = True
+    kind = None
+    alpha = 0.0
+
+    def __init__(self, layer_name):
+        super().__init__(layer_name)
+        self._state = None  # a training forward's record: (BNOut or None, input tensor, shape, storage type)
+
+    def __repr__(self):
+        return "{}({})".format(type(self).__name__, self.layer_name)
+
+    def _name(self):
+        return "{}({})".format(type(self).__name__, self.layer_name)
+
+    def forward(self, X, test_mode=False):
+        self._require_on_gpu()
+        if isinstance(X, JoinOut):
+            X = X.materialize()
+        bn = X if isinstance(X, BNOut) else None
+        x = bn.x if bn is not None else X
+        dtype = act_dtype(x)
+        if len(x.shape) == 4:
+            x = to_nhwc(as_device(x, dtype))
+            y = empty_nhwc(*x.shape, dtype=x.dtype)
+        elif len(x.shape) == 2:
+            if dtype == BF16:
+                raise ValueError("{}: bf16 storage is taken for 4-D maps only".format(self._name()))
+            x = rows(as_device(x, dtype))
+            y = torch.empty_like(x)
+        else:
+            raise ValueError("{}: expected 2-D rows or a 4-D map, got shape {}".format(self._name(), tuple(x.shape)))
+        plain, bnx = _ACT_FWD[x.dtype]
+        if bn is not None:
+            getattr(lib, bnx)(x.data_ptr(), x.numel(), x.shape[1], *bn.bn_args(), self.kind, self.alpha, y.data_ptr(),
+                              stream_handle())
+        else:
+            getattr(lib, plain)(x.data_ptr(), x.numel(), self.kind, self.alpha, y.data_ptr(), stream_handle())
+        if not test_mode:
+            self._state = (bn, x, tuple(x.shape), x.dtype)
+        return y
+
+    def backward(self, upstream_dx):
+        self._require_on_gpu()
+        if self._state is None:
+            raise RuntimeError("{}: backward needs a training-mode forward first (a test-mode forward records "
+                               "nothing)".format(self._name()))
+        bn, x, shape, dtype = self._state
+        if lattice_tag(upstream_dx):
+            raise ValueError("{}: a lattice-form gradient cannot be taken".format(self._name()))
+        if act_dtype(upstream_dx) != dtype:
+            raise ValueError("{} backward of mixed storage types: {} input vs {} gradient".format(
+                self._name(), dtype, act_dtype(upstream_dx)))
+        if tuple(upstream_dx.shape) != shape:
+            raise ValueError("{} backward shape mismatch: {} vs {}".format(self._name(), tuple(upstream_dx.shape),
+                                                                           shape))
+        if len(shape) == 4:
+            dy = to_nhwc(as_device(upstream_dx, dtype))
+            dx = empty_nhwc(*shape, dtype=dtype)
+        else:
+            dy = rows(as_device(upstream_dx, dtype))
+            dx = torch.empty_like(dy)
+        plain, bnx = _ACT_BWD[dtype]
+        if bn is not None:
+            # the gradient w.r.t. the BNOut, and stage 1 of its owner's backward on the same pass
+            C = shape[1]
+            P = x.numel() // C
+            args = bn.bn_args()  # (raises on a stale BNOut before anything is armed)
+            nb = lib.dk_bn_workspace_bytes(P, C)
+            part = Partials(bn, lib.dk_bn_partial_blocks(P, C), C, dy.device)
+            r = getattr(lib, bnx)(x.data_ptr(), dy.data_ptr(), P, C, *args, self.kind, self.alpha, dx.data_ptr(),
+                                  part.ptr, nb, stream_handle())
+            part.hand(dx, r)
+            return dx
+        getattr(lib, plain)(x.data_ptr(), dy.data_ptr(), dy.numel(), self.kind, self.alpha, dx.data_ptr(),
+                            stream_handle())
+        return dx
+
+    def save_to_h5(self, open_f, save_grads=True):
+        from ..network.checkpoint import save_layer
+        save_layer(self, open_f, save_grads)
+
+    def load_from_h5(self, open_f, load_grads=True):
+        from ..network.checkpoint import load_layer
+        load_layer(self, open_f, load_grads)
+
+
+class LeakyReLu(_Activation):
+    """y = v > 0 ? v : alpha * v; the derivative at 0 is alpha (torch.nn.functional.leaky_relu)."""
+    kind = ACT_LEAKY
+
+    def __init__(self, layer_name, alpha=0.01):
+        super().__init__(layer_name)
+        self.alpha = checked_alpha(layer_name, alpha)
+
+    def __repr__(self):
+        return "LeakyReLu({}, alpha={})".format(self.layer_name, self.alpha)
+
+
+class ReLu6(_Activation):
+    """y = min(max(v, 0), 6); the derivative is 1 iff 0 < v < 6 (torch.nn.functional.relu6)."""
+    kind = ACT_RELU6
+
+
+class HardSwish(_Activation):
+    """y = v * min(max(v + 3, 0), 6) / 6; the derivative is 0 for v <= -3, (2 v + 3) / 6 on (-3, 3), 1 for v >= 3
+    (torch.nn.functional.hardswish, whose backward takes the open interval)."""
+    kind = ACT_HARDSWISH
+
+
+class SiLu(_Activation):
+    """y = v * s(v), s(v) = 1 / (1 + e^-v); the derivative is s (1 + v (1 - s)) (torch.nn.functional.silu)."""
+    kind = ACT_SILU

@@ -12,7 +12,8 @@ Layout (one HDF5 file per network, every layer's objects under its ``layer_name`
 
 - ``<name>/layer_info``: an empty float32 dataset whose attributes describe the layer
   (``type`` = class name, plus the constructor's shape / stride / padding / bias fields; for the
-  extension ``DropoutLayer`` its ``drop_prob``, ``seed`` and the ``step`` of its next mask);
+  extension ``DropoutLayer`` its ``drop_prob``, ``seed`` and the ``step`` of its next mask, for the
+  extension ``LeakyReLu`` its ``alpha``);
 - ``<name>/weights`` and ``<name>/bias`` (conv, depthwise, pointwise, dense), or
   ``<name>/gamma``, ``<name>/beta``, ``<name>/running_mean``, ``<name>/running_std`` (BN);
 - ``<name>/grads/<param>`` when ``save_grads`` (the default);
@@ -327,8 +328,21 @@ def _load_dropout(layer, open_f, load_grads):
     layer._state = None
 
 
+def _save_leaky(layer, open_f, save_grads):
+    """An extension (the reference has only ReLu): `alpha` is the layer's one setting."""
+    d = _info(open_f, layer)
+    d.attrs["alpha"] = float(layer.alpha)
+
+
+def _load_leaky(layer, open_f, load_grads):
+    from ..layers.activations import checked_alpha
+    a = _attrs(open_f, layer)
+    layer.alpha = checked_alpha(layer.layer_name, float(a["alpha"]))
+    layer._state = None
+
+
 def _new_layer(l_type, name):
-    from ..layers.activations import ReLu
+    from ..layers.activations import HardSwish, LeakyReLu, ReLu, ReLu6, SiLu
     from ..layers.batch_norm import BatchNormLayer
     from ..layers.convolution import ConvLayer
     from ..layers.dense_layer import DenseLayer
@@ -341,7 +355,8 @@ def _new_layer(l_type, name):
     from ..layers.residual_block import ResidualBlock
     classes = {c.__name__: c for c in (ConvLayer, BatchNormLayer, ReLu, DepthwiseConvLayer, PointwiseConvLayer,
                                        GlobalAveragePoolingLayer, MaxPoolLayer, ReshapeLayer, DropoutLayer,
-                                       DenseLayer, ResidualBlock, SoftmaxWithCrossEntropy)}
+                                       DenseLayer, ResidualBlock, SoftmaxWithCrossEntropy, LeakyReLu, ReLu6,
+                                       HardSwish, SiLu)}
     if l_type not in classes:
         raise ValueError("unknown layer type {!r} for layer {!r}".format(l_type, name))
     return classes[l_type](name)
@@ -402,6 +417,10 @@ _HANDLERS = {
     "DenseLayer": (_save_dense, _load_dense),
     "BatchNormLayer": (_save_bn, _load_bn),
     "ReLu": (_save_plain, _load_plain),
+    "LeakyReLu": (_save_leaky, _load_leaky),
+    "ReLu6": (_save_plain, _load_plain),
+    "HardSwish": (_save_plain, _load_plain),
+    "SiLu": (_save_plain, _load_plain),
     "GlobalAveragePoolingLayer": (_save_plain, _load_plain),
     "MaxPoolLayer": (_save_maxpool, _load_maxpool),
     "ReshapeLayer": (_save_reshape, _load_reshape),

@@ -298,6 +298,38 @@ MODEL["dk_bn_add_bf16"] = lambda a, am, ai, ag, ab, ar, b, bm, bi, bg, bb, br, n
     n * (1 + 4 * (bool(am) + bool(bm))), 2 * 3 * n + (n if mask else 0))
 MODEL["dk_relu_bwd_bn_partial_bf16"] = lambda dy, mask, x, P, C, *rest: (4 * P * C, 2 * 3 * P * C + P * C)
 
+
+# The activations beyond ReLU (dk_act_*): 2 accesses per element forward (BatchNorm on load
+# adds none: the normalised tensor is never written or read), 3 backward (the input, or the BatchNorm's raw input,
+# dy, and dx); dk_act_bwd_bnx_* also writes the fp64 partial rows [rows][2][C] of the BatchNorm's backward.
+_ACT_FLOPS = (1, 2, 4, 40)   # LeakyReLu, ReLu6, HardSwish, SiLu: fp32 operations per element, forward
+_ACT_BWD_FLOPS = (1, 2, 4, 46)
+
+
+def _act_flops(table, kind):
+    return table[kind] if 0 <= kind < len(table) else 0
+
+
+def bn_partial_rows(P, C):
+    """dk_bn_partial_blocks(P, C): the partial rows of the BatchNorm reduce passes (batchnorm.hip bn_blocks)."""
+    groups = C // 4 if C % 4 == 0 else C
+    lanes = 256 // min(groups, 256)
+    return min(max(-(-P // (lanes * 32)), 1), 1024)
+
+
+def _act_entries(suffix, e):
+    MODEL["dk_act_fwd" + suffix] = lambda x, n, kind, alpha, y, st: (n * _act_flops(_ACT_FLOPS, kind), e * 2 * n)
+    MODEL["dk_act_fwd_bnx" + suffix] = lambda x, n, C, m, i, g, b, r, kind, alpha, y, st: (
+        n * (4 + _act_flops(_ACT_FLOPS, kind)), e * 2 * n)
+    MODEL["dk_act_bwd" + suffix] = lambda x, dy, n, kind, alpha, dx, st: (
+        n * _act_flops(_ACT_BWD_FLOPS, kind), e * 3 * n)
+    MODEL["dk_act_bwd_bnx" + suffix] = lambda x, dy, P, C, m, i, g, b, r, kind, alpha, gout, part, nb, st: (
+        P * C * (10 + _act_flops(_ACT_BWD_FLOPS, kind)), e * 3 * P * C + bn_partial_rows(P, C) * 2 * C * 8)
+
+
+_act_entries("_f32", E)
+_act_entries("_bf16", 2)
+
 # host-side queries of the bf16 entries: no device work
 for _n in ("dk_conv2d_fwd_bf16_stats_rows", "dk_conv2d_wgrad_bf16_workspace_bytes", "dk_pwconv_dgrad_bf16_stats_rows"):
     MODEL[_n] = lambda *a: (0, 0)

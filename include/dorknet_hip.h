@@ -622,6 +622,35 @@ int dk_dropout_fwd_bnx_f32(const float* x, long long n, int threshold, long long
 int dk_dropout_fwd_bnx_bf16(const uint16_t* x, long long n, int threshold, long long seed, long long step, int lane, long long first_index, int C, const float* bn_mean, const float* bn_invstd, const float* bn_gamma, const float* bn_beta, int bn_relu, uint16_t* y, void* stream);
 int dk_dropout_bwd_f32(const float* dy, long long n, int threshold, long long seed, long long step, int lane, long long first_index, float* dx, void* stream);
 int dk_dropout_bwd_bf16(const uint16_t* dy, long long n, int threshold, long long seed, long long step, int lane, long long first_index, uint16_t* dx, void* stream);
+/* Activations beyond ReLU (extensions, layers/activations.py; dorknet_amd/csrc/act_math.h, activations.hip;
+ * DESIGN.md section 23).  kind: 0 LeakyReLu (v > 0 ? v : alpha v), 1 ReLu6 (min(max(v, 0), 6)), 2 HardSwish
+ * (v min(max(v + 3, 0), 6) / 6), 3 SiLu (v / (1 + e^-v)); alpha is read by kind 0 only and must be finite.  Every
+ * fp32 operation is rounded once on its own (no contraction), SiLu's exponential is restated from + - * / and
+ * integer operations: tests/_activation_twin.py reproduces every entry bit for bit.  bf16 storage: operands widened,
+ * the fp32 rule applied, one round-to-nearest-even per stored element.  No mask is stored: the backward recomputes
+ * act'(v) from the layer's input.
+ *   dk_act_fwd_*:     y = act(x).
+ *   dk_act_fwd_bnx_*: y = act(v), v = BN(x) [+ ReLU] formed on load (dk_bn_apply_*'s arithmetic, for bf16 rounded
+ *     to bf16 first): bit-identical to apply-then-activate.  The channel of element k is k % C; n % C == 0.
+ *   dk_act_bwd_*:     dx = dy * act'(x).
+ *   dk_act_bwd_bnx_*: x is the BatchNorm's raw input [P][C]; v is recomputed bit for bit, g = dy * act'(v) -- zero
+ *     where a fused ReLU (bn_relu) killed v -- is the gradient w.r.t. the BatchNorm's output, and part[rows][2][C]
+ *     (fp64; rows = dk_bn_partial_blocks(P, C), bytes = dk_bn_workspace_bytes(P, C)) = (sum g, sum g x_hat) over
+ *     the stored g is stage 1 of that BatchNorm's backward, as dk_relu_bwd_bn_partial_* writes it.  Takes an
+ *     in-launch fold arming (dk_bn_fold_arm_bwd) and then returns DK_FOLDED.
+ * Every output element is written exactly once.  16-byte accesses when the tensors (and, for _bnx_, the parameters,
+ * with C % 4 == 0) are 16-byte aligned -- dk_act_bwd_bnx_*: C % 4 == 0 and 16-byte (bf16 8-byte) aligned tensors --
+ * element by element otherwise (fp32; bf16 returns DK_ERR_ARGS) and on the n % 8 tail.
+ * DK_ERR_ARGS: a NULL tensor, n < 1 (P < 1, C < 1), a kind outside 0..3, an alpha that is not finite;
+ * DK_ERR_WORKSPACE: part_bytes too small (nothing is written). */
+int dk_act_fwd_f32(const float* x, long long n, int kind, float alpha, float* y, void* stream);
+int dk_act_fwd_bf16(const uint16_t* x, long long n, int kind, float alpha, uint16_t* y, void* stream);
+int dk_act_fwd_bnx_f32(const float* x, long long n, int C, const float* bn_mean, const float* bn_invstd, const float* bn_gamma, const float* bn_beta, int bn_relu, int kind, float alpha, float* y, void* stream);
+int dk_act_fwd_bnx_bf16(const uint16_t* x, long long n, int C, const float* bn_mean, const float* bn_invstd, const float* bn_gamma, const float* bn_beta, int bn_relu, int kind, float alpha, uint16_t* y, void* stream);
+int dk_act_bwd_f32(const float* x, const float* dy, long long n, int kind, float alpha, float* dx, void* stream);
+int dk_act_bwd_bf16(const uint16_t* x, const uint16_t* dy, long long n, int kind, float alpha, uint16_t* dx, void* stream);
+int dk_act_bwd_bnx_f32(const float* x, const float* dy, int P, int C, const float* bn_mean, const float* bn_invstd, const float* bn_gamma, const float* bn_beta, int bn_relu, int kind, float alpha, float* g, void* part, size_t part_bytes, void* stream);
+int dk_act_bwd_bnx_bf16(const uint16_t* x, const uint16_t* dy, int P, int C, const float* bn_mean, const float* bn_invstd, const float* bn_gamma, const float* bn_beta, int bn_relu, int kind, float alpha, uint16_t* g, void* part, size_t part_bytes, void* stream);
 int dk_softmax_xent_fwd_f32(const float* x, const float* y_onehot, int B, int K, float* p, float* loss, void* stream);
 int dk_softmax_xent_bwd_f32(const float* p, const float* y_onehot, int B, int K, float* dx, void* stream);
 
